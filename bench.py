@@ -6,6 +6,13 @@ sample decode) over one synthetic file image that is already resident in HBM:
 BASELINE.json configs[1], "synthetic 8 GiB single-thread VDIF, 2-bit real,
 1 channel, EDV 0" (8032-byte frames, 32000 samples per frame).
 
+A plain run (``python bench.py --gpus N --steps K --warmup W``) does only what
+the headline needs: it sets up, warms up, times the K steps, writes the last
+step's outputs when ``--dump-outputs DIR`` is given (bench_legs/dump.py) and
+prints the line.  Everything else it measures or checks -- the keys listed
+below, the HBM counter passes and the in-bench spot check -- runs with
+``--full`` only.
+
 ``python bench.py --gpus N``: one process per GPU.  Under
 ``python -m torch.distributed.run`` (the driver's way) the ranks come from the
 environment; started plainly with N > 1 this process -- before it touches the
@@ -16,7 +23,8 @@ scaling, no data-path collective: frames are independent, SURVEY.md section
 
 Besides the contract's keys the line carries
   roofline      dominant kernel (named by the library: bb_last_kernel) timed
-                with HIP events on the launching stream; `traffic` = HBM bytes
+                with HIP events on the launching stream (every run); with
+                --full also `traffic` = HBM bytes
                 per launch from two rocprofv3 --pmc child passes of this same
                 script (run before this process touches the GPU), or the
                 committed profiles/traffic_latest.json when that fails
@@ -81,6 +89,7 @@ from bench_legs.pipeline import pinned_h2d_rate, leg_pipeline                   
 from bench_legs.mid_size import leg_mid_size                                     # noqa: E402,F401
 from bench_legs.cold_read import leg_cold_first_read                             # noqa: E402,F401
 from bench_legs.arena_headline import leg_arena_headline                         # noqa: E402,F401
+from bench_legs.dump import dump_outputs, DUMP_BUDGET_BYTES                     # noqa: E402,F401
 
 
 def main():
@@ -91,13 +100,23 @@ def main():
     ap.add_argument('--gib', type=float, default=8.0, help="file image size per GPU")
     ap.add_argument('--cfg3-gib', type=float, default=8.0, help="cfg3 leg: file bytes per GPU")
     ap.add_argument('--pipeline-gib', type=float, default=2.0, help="pipeline leg: size of each temporary file")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--traffic', choices=('live', 'file', 'none'), default='live')
+    ap.add_argument('--full', action='store_true',
+                    help="besides the headline, run everything else the benchmark measures and checks: the CPU "
+                         "baseline, the HBM counter passes, the spot check and every extra leg (off by default; "
+                         "--no-cpu-baseline / --traffic / --no-extra-legs / --legs narrow it)")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="after the timed steps write what the last step computed (decoded samples, frame "
+                         "index, scan records; a fixed stratified sample of the larger ones, 60 MiB in all) "
+                         "as DIR/<name>.npy in float32 / float64")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help="with --full: no CPU baseline")
+    ap.add_argument('--traffic', choices=('live', 'file', 'none'), default=None,
+                    help="with --full: where the HBM bytes come from (default live)")
     ap.add_argument('--no-extra-legs', action='store_true',
-                    help="skip api_read / cfg3 / other_configs (headline only); same as --legs headline")
+                    help="with --full: skip api_read / cfg3 / other_configs (headline only); same as --legs headline")
     ap.add_argument('--legs', choices=('all', 'headline', 'cfg3'), default='all',
-                    help="all (default); headline: the headline step only, no CPU baseline, no counter passes "
-                         "(an N-GPU run finishes in well under a minute); cfg3: headline + the cfg3 leg")
+                    help="with --full: all (default); headline: the headline step only, no CPU baseline, no "
+                         "counter passes (an N-GPU run finishes in well under a minute); cfg3: headline + the "
+                         "cfg3 leg")
     ap.add_argument('--pmc-child', action='store_true',
                     help="internal: headline kernel only, no JSON extras (run under rocprofv3 --pmc)")
     ap.add_argument('--force-dist', action='store_true',
@@ -108,6 +127,15 @@ def main():
     ap.add_argument('--dry-run', action='store_true',
                     help="CPU rehearsal of the multi-rank plumbing with gloo (no GPU, no measurement)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full and not args.pmc_child:
+        if args.legs == 'cfg3' or args.traffic in ('live', 'file'):
+            ap.error("--legs cfg3 and --traffic live / file belong to a --full run")
+        # a plain run: the headline only
+        args.legs = 'headline'
+    if args.traffic is None:
+        args.traffic = 'live'
     if args.pmc_child:
         args.no_cpu_baseline, args.no_extra_legs, args.traffic = True, True, 'none'
     if args.legs == 'headline':
@@ -242,12 +270,12 @@ def main():
     torch.cuda.synchronize()
     kernel_name = _lib.last_kernel()
 
-    # sanity spot check (outside the timed region; NOT the parity proof, which
-    # lives in tests/): three frames re-expanded on the host from the library's
-    # own level table
-    lev = _lib.get_levels(_lib.CODER_VDIF, 2)
+    # sanity spot check (--full; outside the timed region; NOT the parity proof,
+    # which lives in tests/): three frames re-expanded on the host from the
+    # library's own level table
     ok = True
-    if args.warmup:
+    if args.full and args.warmup:
+        lev = _lib.get_levels(_lib.CODER_VDIF, 2)
         for f in (0, nframes // 3, nframes - 1):
             raw = image[f * FRAME_NBYTES + HEADER_NBYTES:(f + 1) * FRAME_NBYTES].cpu().numpy()
             got = out[f * SPF:(f + 1) * SPF].cpu().numpy()
@@ -258,7 +286,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for k in range(args.steps):
-        step(k)
+        last = step(k)
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
@@ -275,6 +303,19 @@ def main():
         per_rank = [float(x.item()) for x in allk]
     if args.pmc_child:
         return
+    if args.dump_outputs:
+        # what a caller of the timed path receives from its last step, taken
+        # before the extra legs of --full write into `out`; the inputs are
+        # seeded, so the same arguments give the same files
+        recs, src = last
+        sfx = "_rank{}".format(rank) if world > 1 else ""
+        written = dump_outputs(args.dump_outputs,
+                               {"decoded_samples" + sfx: (out, np.float32),
+                                "frame_index" + sfx: (src, np.float64),
+                                "scan_records" + sfx: (recs, np.float64)},
+                               budget=DUMP_BUDGET_BYTES // world)
+        for name, what in written.items():
+            print("bench.py: dumped {}.npy: {}".format(name, what), file=sys.stderr)
 
     achieved = alg_bytes / (kern_avg * 1e-3) / 1e9
     total_samples = nframes * SPF * world * args.steps
@@ -314,8 +355,9 @@ def main():
                      "kernel_ms_avg": round(kern_avg, 4),
                      "algorithmic_bytes_per_launch": alg_bytes,
                      "traffic": traffic, "traffic_detail": traffic_detail},
-        "sanity_spot_check": ok,
     }
+    if args.full:
+        line["sanity_spot_check"] = ok
     if per_rank is not None:
         line["per_rank"] = {"kernel_ms_avg": [round(x, 4) for x in per_rank],
                             "roofline_frac": [round(alg_bytes / (x * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)

@@ -28,7 +28,8 @@ def collect_checks(line):
             v = v.get(k) if isinstance(v, dict) else None
         checks[name] = v is True
 
-    put("headline.sanity_spot_check", line, "sanity_spot_check")
+    if "sanity_spot_check" in line:                 # (--full runs only)
+        put("headline.sanity_spot_check", line, "sanity_spot_check")
     if "parity_digests" in line:
         put("parity_digests.all_match", line, "parity_digests", "all_match")
     if "invalid_fill" in line:

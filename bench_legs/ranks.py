@@ -66,7 +66,9 @@ def dry_run(args, rank, world):
     """CPU rehearsal of the multi-rank plumbing (tests/test_bench_cli.py): gloo
     rendezvous, slab partition, the index broadcast, barrier + max-over-ranks
     timing, one JSON line from rank 0.  Nothing is decoded and nothing is
-    measured: ``value`` is null and ``dry_run`` is true."""
+    measured: ``value`` is null and ``dry_run`` is true.  As in a real run the
+    cfg3 leg (here: its index broadcast) and a CPU baseline handed over by the
+    parent belong to ``--full``."""
     import torch.distributed as dist
     from baseband_amd.parallel import frame_slab, broadcast_frame_index
     if world > 1:
@@ -74,14 +76,16 @@ def dry_run(args, rank, world):
         dist.init_process_group('gloo')
     nsets = 1000 * world
     lo, hi = frame_slab(nsets, rank, world)
-    src = torch.arange(nsets * CFG3_THREADS, dtype=torch.int64) * FRAME_NBYTES + HEADER_NBYTES \
-        if rank == 0 else None
-    t0 = time.perf_counter()
-    if world > 1:
-        src = broadcast_frame_index(src, nsets * CFG3_THREADS, src_rank=0)
-    coll_ms = (time.perf_counter() - t0) * 1e3
-    ok = bool((src[lo * CFG3_THREADS:hi * CFG3_THREADS]
-               == torch.arange(lo * CFG3_THREADS, hi * CFG3_THREADS) * FRAME_NBYTES + HEADER_NBYTES).all())
+    cfg3 = args.full and args.legs in ('all', 'cfg3') and not args.no_extra_legs
+    if cfg3:
+        src = torch.arange(nsets * CFG3_THREADS, dtype=torch.int64) * FRAME_NBYTES + HEADER_NBYTES \
+            if rank == 0 else None
+        t0 = time.perf_counter()
+        if world > 1:
+            src = broadcast_frame_index(src, nsets * CFG3_THREADS, src_rank=0)
+        coll_ms = (time.perf_counter() - t0) * 1e3
+        ok = bool((src[lo * CFG3_THREADS:hi * CFG3_THREADS]
+                   == torch.arange(lo * CFG3_THREADS, hi * CFG3_THREADS) * FRAME_NBYTES + HEADER_NBYTES).all())
     seen = torch.ones(1)
     mine = torch.tensor([0.001 * (rank + 1)], dtype=torch.float64)
     elapsed = mine.clone()
@@ -95,12 +99,11 @@ def dry_run(args, rank, world):
     if rank == 0:
         cpu = None
         handed = os.environ.get(CPU_JSON_ENV)
-        if handed and os.path.exists(handed):       # what the parent of an N > 1 run timed
-            with open(handed) as f:
+        if args.full and not args.no_cpu_baseline and handed and os.path.exists(handed):
+            with open(handed) as f:                 # what the parent of an N > 1 run timed
                 cpu = json.load(f)
-        rc = finish({
+        line = {
             "metric": "decoded Msamples/s, VDIF 2-bit 1-thread (scan + index + decode, input resident in HBM)",
-            "sanity_spot_check": True,              # nothing is decoded in a dry run
             "cpu_baseline": cpu,
             "roofline": {"traffic": None, "traffic_detail": {
                 "hbm_bytes_per_launch": None, "reason": "dry run" if world == 1 else "counter passes run at N = 1 only"}},
@@ -109,11 +112,15 @@ def dry_run(args, rank, world):
             "scaling": "weak", "vs_baseline": None, "dtype": "float32", "data": "synthetic",
             "dry_run": True, "ranks_seen": int(seen.item()), "slab_of_rank0": [lo, hi],
             "max_over_ranks_s": float(elapsed.item()),
-            "per_rank": {"kernel_ms_avg": [round(float(x.item()) * 1e3, 4) for x in per_rank]},
-            "cfg3": {"rank0_footprint_GiB": rank0_footprint_gib(args.cfg3_gib, world),
-                     "collective": {"bytes": nsets * CFG3_THREADS * 8, "ms": round(coll_ms, 3),
-                                    "ranks_seen": int(seen.item()), "backend": "gloo"},
-                     "index_ok": ok}}, args.detail)
+            "per_rank": {"kernel_ms_avg": [round(float(x.item()) * 1e3, 4) for x in per_rank]}}
+        if args.full:
+            line["sanity_spot_check"] = True        # (nothing is decoded in a dry run)
+        if cfg3:
+            line["cfg3"] = {"rank0_footprint_GiB": rank0_footprint_gib(args.cfg3_gib, world),
+                            "collective": {"bytes": nsets * CFG3_THREADS * 8, "ms": round(coll_ms, 3),
+                                           "ranks_seen": int(seen.item()), "backend": "gloo"},
+                            "index_ok": ok}
+        rc = finish(line, args.detail)
     else:
         rc = 0
     if world > 1:

@@ -1,7 +1,8 @@
 """bench.py's multi-rank plumbing on the CPU: ``python bench.py --gpus 2
 --dry-run`` must start two ranks itself (no launcher, no WORLD_SIZE in the
-environment), rendezvous over gloo on 127.0.0.1, broadcast the frame index and
-print ONE JSON line with ``n_gpus == 2`` from rank 0.  Nothing is decoded in
+environment), rendezvous over gloo on 127.0.0.1, broadcast the frame index
+(``--full``: the cfg3 leg) and print ONE JSON line with ``n_gpus == 2`` from
+rank 0.  Nothing is decoded in
 this mode (no GPU here); the line says so (``dry_run``, ``value`` null).
 
 The line is COMPACT (the driver keeps the tail of stdout
@@ -46,7 +47,7 @@ def _check_compact(stdout):
 
 def test_gpus_2_spawns_two_ranks_and_prints_one_line(tmp_path):
     detail = tmp_path / 'd.json'
-    r, lines = _run(['--gpus', '2', '--steps', '3', '--warmup', '1', '--dry-run'], detail=detail)
+    r, lines = _run(['--gpus', '2', '--steps', '3', '--warmup', '1', '--dry-run', '--full'], detail=detail)
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(lines) == 1, r.stdout
     line = _check_compact(r.stdout)
@@ -99,7 +100,7 @@ def test_under_torch_distributed_run_like_the_driver(tmp_path):
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
                         '--master-addr', '127.0.0.1', '--master-port', str(port),
                         os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
-                        '--dry-run', '--detail', str(tmp_path / 'd.json')],
+                        '--dry-run', '--full', '--detail', str(tmp_path / 'd.json')],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -130,7 +131,7 @@ def test_world_8_exactly_as_the_driver_starts_it(tmp_path):
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '8',
                         '--master-addr', '127.0.0.1', '--master-port', str(port),
                         os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '1',
-                        '--dry-run', '--detail', str(tmp_path / 'd8.json')],
+                        '--dry-run', '--full', '--detail', str(tmp_path / 'd8.json')],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -155,18 +156,19 @@ def test_a_false_self_check_fails_the_bench(tmp_path):
     still printed).  One rank and two ranks (the launcher must pass rank 0's
     status on)."""
     detail = tmp_path / 'd.json'
-    r, lines = _run(['--dry-run'], detail=detail)
+    r, lines = _run(['--dry-run', '--full'], detail=detail)
     assert r.returncode == 0
     line = json.loads(lines[0])
     assert line['checks_ok'] is True and 'failed_checks' not in line
     assert json.loads(detail.read_text())['checks']['cfg3.index_ok'] is True
-    r, lines = _run(['--dry-run'], {'BB_BENCH_FORCE_CHECK_FALSE': 'cfg3.index_ok'}, detail=detail)
+    r, lines = _run(['--dry-run', '--full'], {'BB_BENCH_FORCE_CHECK_FALSE': 'cfg3.index_ok'}, detail=detail)
     assert r.returncode == 3, (r.returncode, r.stderr[-500:])
     line = _check_compact(r.stdout)
     assert line['checks_ok'] is False and line['failed_checks'] == ['cfg3.index_ok']
     assert json.loads(detail.read_text())['checks']['cfg3.index_ok'] is False
     assert 'self-checks FAILED' in r.stderr and 'cfg3.index_ok' in r.stderr
-    r, lines = _run(['--gpus', '2', '--dry-run'], {'BB_BENCH_FORCE_CHECK_FALSE': 'cfg3.index_ok'}, detail=detail)
+    r, lines = _run(['--gpus', '2', '--dry-run', '--full'], {'BB_BENCH_FORCE_CHECK_FALSE': 'cfg3.index_ok'},
+                    detail=detail)
     assert r.returncode != 0 and len(lines) == 1
     assert json.loads(lines[0])['checks_ok'] is False
 
@@ -239,3 +241,61 @@ def test_physical_core_count_is_stated():
     import bench
     nphys, nlog = bench.physical_cores()
     assert 1 <= nphys <= nlog == len(os.sched_getaffinity(0))
+
+
+def test_a_plain_run_is_the_headline_only(tmp_path):
+    """Without ``--full`` a run does only what the headline needs: no cfg3 leg (no
+    index broadcast), no CPU baseline even when a parent handed one over, no spot
+    check; options that select the extras need ``--full``; ``--steps`` is at least 1."""
+    handed = tmp_path / 'cpu.json'
+    handed.write_text(json.dumps({"value": 123.5, "unit": "Msamples/s", "cores": 1, "kind": "port"}))
+    detail = tmp_path / 'd.json'
+    r, lines = _run(['--gpus', '2', '--steps', '3', '--warmup', '1', '--dry-run'],
+                    {'BB_BENCH_CPU_BASELINE_JSON': str(handed)}, detail=detail)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert len(lines) == 1, r.stdout
+    line = _check_compact(r.stdout)
+    assert line['n_gpus'] == 2 and line['ranks_seen'] == 2 and line['steps'] == 3
+    assert line['cpu_baseline'] is None and 'cfg3' not in line and line['checks_ok'] is True
+    full = json.loads(detail.read_text())
+    assert 'cfg3' not in full and 'sanity_spot_check' not in full and full['checks'] == {}
+    for argv in (['--legs', 'cfg3'], ['--traffic', 'live'], ['--steps', '0']):
+        r, lines = _run(['--dry-run'] + argv)
+        assert r.returncode == 2 and not lines, argv
+    r, lines = _run(['--dry-run', '--full', '--legs', 'headline'], detail=detail)
+    assert r.returncode == 0 and 'cfg3' not in json.loads(lines[0])
+
+
+def test_dump_outputs_are_fixed_bounded_float_files(tmp_path):
+    """``--dump-outputs``: float32 / float64 .npy files only, within the byte
+    budget, an array that fits written whole, a larger one as a stratified
+    sample (one element per stratum) at the same positions in every run."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    from bench_legs.dump import dump_outputs, sample_positions
+    pos = sample_positions(1000003, 1000)
+    assert torch.equal(pos, sample_positions(1000003, 1000))
+    stride = -(-1000003 // 1000)
+    assert pos.numel() == 1000 and bool((pos // stride == torch.arange(1000)).all()) and int(pos[-1]) < 1000003
+    assert torch.equal(sample_positions(10, 20), torch.arange(10))
+    samples = torch.randn(3 * 2 ** 20)
+    index = torch.arange(5000, dtype=torch.int64) * 8032 + 32
+    recs = torch.randint(-2 ** 31, 2 ** 31 - 1, (2 ** 20, 4), dtype=torch.int64).to(torch.int32)
+    arrays = {"decoded_samples": (samples, np.float32), "frame_index": (index, np.float64),
+              "scan_records": (recs, np.float64)}
+    budget = 8 * 2 ** 20
+    for d in ('a', 'b'):
+        dump_outputs(str(tmp_path / d), arrays, budget=budget)
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == ['decoded_samples.npy', 'frame_index.npy', 'scan_records.npy']
+    assert sum(os.path.getsize(tmp_path / 'a' / n) for n in names) <= budget + 3 * 128
+    for n in names:
+        a, b = np.load(tmp_path / 'a' / n), np.load(tmp_path / 'b' / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    idx = np.load(tmp_path / 'a' / 'frame_index.npy')
+    assert idx.dtype == np.float64 and np.array_equal(idx, index.numpy().astype(np.float64))
+    got = np.load(tmp_path / 'a' / 'decoded_samples.npy')
+    assert got.dtype == np.float32 and 0 < got.size < samples.numel()
+    pos = sample_positions(samples.numel(), got.size)
+    assert np.array_equal(got, samples[pos].numpy())
