@@ -195,12 +195,20 @@ class GPUStreamWriterBase:
         want = torch.complex64 if self.complex_data else torch.float32
         data = data.to(device='cuda', dtype=want).reshape(
             (data.shape[0],) + self._unsliced_shape)
+        # `data` may be the caller's own tensor (or a view of it): whatever of it
+        # stays pending past this call is cloned -- at most one frame of samples,
+        # queued on the caller's stream, so a refill of the caller's buffer
+        # (``buf.copy_(next); fw.write(buf)``) or any later change of it cannot
+        # reach frames that are encoded at the next write() or at close().
+        # Whole frames are encoded from `data` itself, in stream order.
         self._pending.append((data, bool(valid)))
         self._npending += data.shape[0]
         self.offset += data.shape[0]
         spf = self.samples_per_frame
         nfull = self._npending // spf
-        if nfull:
+        if not nfull:
+            self._pending[-1] = (data.clone(), bool(valid))
+        else:
             block = torch.cat([d for d, _ in self._pending]) if len(self._pending) > 1 \
                 else self._pending[0][0]
             # validity per frame: a frame is valid only if all of its pieces were
@@ -212,6 +220,8 @@ class GPUStreamWriterBase:
             self._write_frames(block[:nfull * spf], flags)
             self._nframes_written += nfull
             rest = block[nfull * spf:]
+            if len(self._pending) == 1 and rest.shape[0]:
+                rest = rest.clone()             # (a torch.cat result is the writer's own)
             tail_ok = self._pending[-1][1]
             self._pending = [(rest, tail_ok)] if rest.shape[0] else []
             self._npending = rest.shape[0]
