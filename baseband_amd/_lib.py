@@ -30,6 +30,11 @@ CODER_VDIF = 0
 CODER_MARK5B = 1
 CODER_INT = 2
 
+# enum bb_out_type (bb_decode_params.out_type)
+OUT_F32 = 0
+OUT_F16 = 1
+OUT_BF16 = 2
+
 FRAME_OK = 0x1
 FRAME_INVALID = 0x2
 
@@ -111,7 +116,7 @@ class DecodeParams(C.Structure):
                 ('nslot', C.c_int32), ('payload_nbytes', C.c_uint64),
                 ('src0', C.c_int64), ('src_stride', C.c_int64),
                 ('complex_data', C.c_int32), ('fill_re', C.c_float),
-                ('fill_im', C.c_float), ('reserved', C.c_int32)]
+                ('fill_im', C.c_float), ('out_type', C.c_int32)]
 
 
 class Mark4ScanParams(C.Structure):
@@ -121,7 +126,7 @@ class Mark4ScanParams(C.Structure):
 
 
 class Mark4DecodeParams(C.Structure):
-    _fields_ = [('ntrack', C.c_int32), ('reserved', C.c_int32),
+    _fields_ = [('ntrack', C.c_int32), ('out_type', C.c_int32),
                 ('nwords', C.c_uint64), ('fill_words', C.c_uint64),
                 ('src0', C.c_int64), ('src_stride', C.c_int64),
                 ('sign_bit', C.c_uint8 * 32), ('mag_bit', C.c_uint8 * 32),
@@ -180,6 +185,8 @@ SIGNATURES = [
     ('bb_last_kernel', C.c_char_p, []),
     ('bb_init', C.c_int, []),
     ('bb_get_levels', C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_float), _sz]),
+    ('bb_get_levels_as', C.c_int, [C.c_int, C.c_int, C.c_int, _vp, _sz]),
+    ('bb_decode_out_check', C.c_int, [C.POINTER(DecodeParams)]),
     ('bb_get_encode_thresholds', C.c_int, [C.POINTER(C.c_float)]),
     ('bb_vdif_scan', C.c_int, [_vp, _sz, C.POINTER(VDIFScanParams), _vp, _sz, _vp]),
     ('bb_vdif_locate', C.c_int, [_vp, _sz, C.POINTER(VDIFScanParams), _vp, _sz, _vp, _vp]),
@@ -261,6 +268,23 @@ def get_levels(coder, bps):
     out = np.empty(n, dtype=np.float32)
     check(lib.bb_get_levels(coder, bps, out.ctypes.data_as(C.POINTER(C.c_float)), n),
           'bb_get_levels')
+    return out
+
+
+def out_type_of(dtype):
+    """torch dtype of decoded samples -> enum bb_out_type (complex types count as
+    their (re, im) element type); None for a type the library does not write."""
+    return {torch.float32: OUT_F32, torch.complex64: OUT_F32, torch.float16: OUT_F16,
+            torch.complex32: OUT_F16, torch.bfloat16: OUT_BF16}.get(dtype)
+
+
+def levels_as(coder, bps, out_type):
+    """Host copy of the code -> level table in an output type: float32 values for
+    OUT_F32, uint16 bit patterns for OUT_F16 / OUT_BF16 (bb_get_levels_as)."""
+    import numpy as np
+    n = 1 << bps
+    out = np.empty(n, dtype=np.float32 if out_type == OUT_F32 else np.uint16)
+    check(lib.bb_get_levels_as(coder, bps, out_type, out.ctypes.data_as(_vp), n), 'bb_get_levels_as')
     return out
 
 

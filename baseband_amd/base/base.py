@@ -859,11 +859,76 @@ class GPUStreamReaderBase:
             seek = self._raw_seek = getattr(raw, 'fh_raw', raw).seek
         seek(self._file_offset0 + ((self.offset - 1) // self.samples_per_frame + 1) * self._set_nbytes)
 
+    # ``fh.sample_dtype = torch.float16`` (or ``torch.bfloat16``; None = float32, as always):
+    # ``read()`` without `out` returns samples of that element type -- ``torch.complex32`` for a
+    # complex stream with float16 -- and the decoded read-ahead window is kept in it.  Where
+    # the library has 16-bit decode kernels for the format (`_half_geometry`) the decode
+    # writes the type itself (half the stores, no float32 copy anywhere); elsewhere the
+    # samples are decoded to float32 and converted.  Same values either way: the float32
+    # sample rounded once to nearest even.  ``fh.dtype`` keeps naming the stream's native
+    # NumPy dtype, as the reference's does; readers with `host_results` ignore the setting.
+    _sample_dtype = None
+
+    @property
+    def sample_dtype(self):
+        return self._sample_dtype
+
+    @sample_dtype.setter
+    def sample_dtype(self, dtype):
+        if dtype is not None and isinstance(dtype, str):
+            dtype = getattr(torch, dtype, dtype)
+        if dtype == torch.float32:
+            dtype = None
+        if dtype not in (None, torch.float16, torch.bfloat16):
+            raise ValueError("sample_dtype is None (float32), torch.float16 or torch.bfloat16, not {!r}".format(dtype))
+        self._refuse_complex_bfloat16(dtype)
+        if dtype != self._sample_dtype:
+            self._decoded = self._decoded_host = None       # (a decoded window is of one type)
+        self._sample_dtype = dtype
+
+    def _refuse_complex_bfloat16(self, dtype):
+        if dtype == torch.bfloat16 and self.complex_data:
+            raise ValueError("this stream is complex and torch has no complex bfloat16 type: "
+                             "use torch.float16 (samples come as torch.complex32) or float32")
+
+    @staticmethod
+    def _out_elem(out):
+        """Element type a caller's `out` asks the decode for (NumPy arrays: float32)."""
+        if isinstance(out, torch.Tensor):
+            if out.dtype in (torch.float16, torch.complex32):
+                return torch.float16
+            if out.dtype == torch.bfloat16:
+                return torch.bfloat16
+        return torch.float32
+
+    def _half_geometry(self):
+        """``(coder, bps, chunk, nslot, payload_nbytes)`` of the decode launches of this
+        reader when they go through bb_decode_frames or a window call built on it, else
+        None: formats whose kernels write float32 only (Mark 4, the int8 transposes,
+        float32 DADA) convert afterwards."""
+        return None
+
+    def _half_direct(self, elem):
+        """May the decode write `elem` (torch.float16 / torch.bfloat16) itself?  Asks the
+        library (bb_decode_out_check); never with a channel subset folded into the
+        decode (the selecting kernels write float32)."""
+        if self._within_np is not None:
+            return False
+        geom = self._half_geometry()
+        key = (geom, elem)
+        cached = self.__dict__.get('_half_direct_cached')
+        if cached is None or cached[0] != key:
+            ok = geom is not None and kernels.out_supported(*geom, elem)
+            cached = self._half_direct_cached = (key, ok)
+        return cached[1]
+
     def read(self, count=None, out=None):
         """Read and decode `count` complete samples -> device tensor of shape
         ``(count,) + sample_shape`` (base/base.py:919-969)."""
         if self.closed:
             raise ValueError("I/O operation on closed stream.")
+        if isinstance(out, torch.Tensor):
+            self._refuse_complex_bfloat16(out.dtype)
         samples_left = self.shape[0] - self.offset
         if out is None:
             if count is None or count < 0:
@@ -879,7 +944,10 @@ class GPUStreamReaderBase:
             warnings.warn(self._pending_warning)
             self._pending_warning = None
         host = self.host_results and out is None
-        ahead = self._from_decoded_ahead(count, host) if count else None
+        # (a decoded window is of ONE element type: it serves results of that type only --
+        # float32 samples are never made from a window that was rounded to 16 bits)
+        ahead = self._from_decoded_ahead(count, host) \
+            if count and (out is None or self._out_elem(out) == self._elem_dtype()) else None
         if ahead is not None:
             self.offset += count
             self._seq_end = self.offset
@@ -966,7 +1034,7 @@ class GPUStreamReaderBase:
             return None
         spf = self.samples_per_frame
         ncomp = 2 if self.complex_data else 1
-        set_bytes = spf * int(np.prod(self._decode_shape)) * ncomp * 4
+        set_bytes = spf * int(np.prod(self._decode_shape)) * ncomp * (4 if self._elem_dtype() == torch.float32 else 2)
         max_sets = max(1, self.decode_ahead_bytes // max(1, set_bytes))
         first = off // spf
         need = -(-(off + count) // spf) - first
@@ -1101,22 +1169,24 @@ class GPUStreamReaderBase:
             o0 = body0 * spf - self.offset
             self._read_sets(body0, body1, flat[o0 * row:(o0 + (body1 - body0) * spf) * row])
             if off0:
-                head = self._squeeze_and_subset(self._read_sets(first, body0))
+                head = self._squeeze_and_subset(self._read_sets_as(first, body0, flat.dtype))
                 out[:o0] = head[off0:]
             if body1 < last:
                 ntail = stop - body1 * spf
-                tail = self._squeeze_and_subset(self._read_sets(body1, last))
+                tail = self._squeeze_and_subset(self._read_sets_as(body1, last, flat.dtype))
                 out[count - ntail:] = tail[:ntail]
             return out, True
-        data = self._read_sets(first, last)
+        data = self._read_sets(first, last) if out is None else self._read_sets_as(first, last, self._out_elem(out))
         return data[off0:off0 + count], False
 
     def _direct_target(self, out):
-        """Flat float32 view of `out` when the decode may write straight into
-        it: a contiguous device tensor of the stream's dtype, and no subset
-        (squeezing only drops unit dimensions)."""
+        """Flat float32 (float16, bfloat16) view of `out` when the decode may write
+        straight into it: a contiguous device tensor of the stream's dtype -- or of
+        one of its 16-bit forms: float16 / bfloat16, complex32 for complex streams
+        -- and no subset (squeezing only drops unit dimensions)."""
         if (not isinstance(out, torch.Tensor) or not out.is_cuda or not out.is_contiguous()
-                or out.dtype != (torch.complex64 if self.complex_data else torch.float32)):
+                or out.dtype not in ((torch.complex64, torch.complex32) if self.complex_data
+                                     else (torch.float32, torch.float16, torch.bfloat16))):
             return None
         if self._within_np is None and (self.subset or getattr(self, '_frameset_subset', None)
                                      or tuple(self._decode_shape) != tuple(self._unsliced_shape)):
@@ -1124,16 +1194,51 @@ class GPUStreamReaderBase:
         flat = torch.view_as_real(out) if self.complex_data else out
         return flat.reshape(-1)
 
+    def _elem_dtype(self):
+        """Element type of what ``read()`` returns without `out`."""
+        if self._sample_dtype is None or self.host_results:
+            return torch.float32
+        return self._sample_dtype
+
+    _want_elem = None       # element type of the `_read_sets` call in progress, when not the default's
+
+    def _read_sets_as(self, first, last, elem):
+        """`_read_sets` into a new tensor of element type `elem`."""
+        self._want_elem = elem
+        try:
+            return self._read_sets(first, last)
+        finally:
+            self._want_elem = None
+
     def _read_sets(self, first, last, into=None):
         """Decode frame sets [first, last) -> tensor (nsets*spf, *unsliced);
-        `into` is an optional flat float32 device tensor to decode into."""
+        `into` is an optional flat device tensor to decode into.  The element
+        type is that of `into`, else what `_read_sets_as` asks for, else
+        `sample_dtype`.  A 16-bit type the format's kernels do not write
+        (`_half_direct`) is decoded to float32 and converted."""
+        elem = into.dtype if into is not None else (self._want_elem or self._elem_dtype())
+        if elem == torch.float32 or self._half_direct(elem):
+            return self._decode_sets(first, last, into, elem)
+        data = self._decode_sets(first, last, None, torch.float32)
+        flat = (torch.view_as_real(data) if self.complex_data else data).reshape(-1)
+        if into is not None:
+            into.copy_(flat)
+            flat = into
+        else:
+            flat = flat.to(elem)
+        if self.complex_data:
+            flat = torch.view_as_complex(flat.view(-1, 2))
+        return flat.reshape(data.shape)
+
+    def _decode_sets(self, first, last, into, elem):
+        """`_read_sets` in an element type the decode writes itself."""
         kernels.require_gpu()
         self._last_scan_side = None
         nsets = last - first
         spf = self.samples_per_frame
         ncomp = 2 if self.complex_data else 1
         row = int(np.prod(self._decode_shape)) * ncomp
-        flat = into if into is not None else empty_output(nsets * spf * row, torch.float32)
+        flat = into if into is not None else kernels.empty_decoded(nsets * spf * row, dtype=elem)
         set_nbytes = self._set_nbytes
         resident = self._resident_bytes() if nsets else None
         if resident is None and nsets and self._have:

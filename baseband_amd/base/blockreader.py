@@ -187,13 +187,20 @@ class BlockStreamReader(GPUStreamReaderBase):
         if count > samples_left:
             raise EOFError("cannot read from beyond end of input.")
         kernels.require_gpu()
+        if isinstance(out, torch.Tensor):
+            self._refuse_complex_bfloat16(out.dtype)
+        # element type of the result (`sample_dtype`, or what a tensor `out` is made of); a 16-bit
+        # type this format's kernels do not write is decoded to float32 and converted at the end
+        elem = self._elem_dtype() if out is None else self._out_elem(out)
+        convert = elem != torch.float32 and not self._half_direct(elem)
         ncomp = 2 if self.complex_data else 1
         row = int(np.prod(self._decode_shape)) * ncomp
         # pieces land exactly where they belong, so a suitable `out` tensor is
         # decoded into directly
         direct = (isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous()
                   and count > 0 and (not self.subset or self._within_np is not None)
-                  and out.dtype == (torch.complex64 if self.complex_data else torch.float32))
+                  and out.dtype in ((torch.complex64, torch.complex32) if self.complex_data
+                                    else (torch.float32, torch.float16, torch.bfloat16)))
         pieces = self._pieces(self.offset, count)
         image = self._image()
         resident = self._resident_bytes()
@@ -207,10 +214,10 @@ class BlockStreamReader(GPUStreamReaderBase):
             hi = min(last_lo + last_n, resident.numel())
             if 2 * count * self._frame_nbytes >= (hi - lo) * self.samples_per_frame:    # (most of it is wanted)
                 kernels.touch(resident, lo, hi - lo)
-        if direct:
+        if direct and not convert:
             flat = (torch.view_as_real(out) if self.complex_data else out).reshape(-1)
         else:
-            flat = empty_output(count * row, torch.float32)
+            flat = kernels.empty_decoded(count * row, dtype=torch.float32 if convert else elem)
         # merge consecutive frames that use the same row range into runs
         runs = []
         for f, a, b in pieces:
@@ -292,8 +299,12 @@ class BlockStreamReader(GPUStreamReaderBase):
             done += (f1 - f0) * (b - a)
         assert done == count
         if direct:
+            if convert:
+                (torch.view_as_real(out) if self.complex_data else out).reshape(-1).copy_(flat)
             self.offset += count
             return out
+        if convert:
+            flat = flat.to(elem)
         if self.complex_data:
             flat = torch.view_as_complex(flat.view(-1, 2))
         data = flat.reshape((count,) + tuple(self._decode_shape))

@@ -159,10 +159,16 @@ class FormatOpener:
                 and source_kind(name) in ('sequence', 'template')
                 and 'file_size' not in kwargs and kwargs.get('header0') is not None):
             kwargs['file_size'] = self.default_file_size(kwargs['header0'])
+        # (a reader ATTRIBUTE that may be given at open, like `fh.sample_dtype = ...` right after
+        # it: taken out before the keywords go on to the header inference and the reader class)
+        sample_dtype = kwargs.pop('sample_dtype', None) if mode == 'rs' else None
         fh, source = self._handle(name, mode, kwargs)
         init_args = dict(kwargs)
         try:
             opened = self.classes[mode](fh, **kwargs)
+            if sample_dtype is not None:
+                opened.sample_dtype = sample_dtype
+                init_args['sample_dtype'] = sample_dtype
         except Exception:
             if fh is not name:
                 try:

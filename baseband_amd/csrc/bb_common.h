@@ -28,6 +28,9 @@ typedef uint32_t bb_u4 __attribute__((ext_vector_type(4)));
 // that they are bit-identical to the NumPy expressions of the reference
 // (base/encoding.py:52-56,141-143).
 __device__ float g_levels[3][4][256];
+// ... and converted to float16 / bfloat16 bit patterns on the host (bbdecode.hip h_levels16):
+// [out_type - 1][coder][log2(bps)][code]
+__device__ uint16_t g_levels16[2][3][4][256];
 
 __device__ __forceinline__ int bb_lane() { return threadIdx.x & (BB_WAVE - 1); }
 __device__ __forceinline__ int bb_wave() { return threadIdx.x / BB_WAVE; }

@@ -9,6 +9,8 @@
 #endif
 #include "k_lut.h"
 #include "k_lds.h"
+#include "k_half.h"
+#include "bb_half_host.h"
 #include "k_copy.h"
 #include "k_tfpick.h"
 #if BB_EXP
@@ -44,6 +46,9 @@ inline int hip_fail(hipError_t e) { t_last_hip = (int)e; return BB_EIO; }
 // ---- level tables ---------------------------------------------------------
 float h_levels[3][4][256];
 float h_enc2_thr[3];
+// the same tables in the 16-bit output types, [BB_OUT_F16 - 1 | BB_OUT_BF16 - 1][coder][log2 bps][code]
+// (round to nearest even, once: bb_half_host.h); what the kernels of k_half.h are handed
+uint16_t h_levels16[2][3][4][256];
 std::once_flag h_levels_once;
 
 // floats in increasing order <-> uint32 keys in increasing order
@@ -105,6 +110,12 @@ void fill_host_levels()
     // two's complement integers (gsb/payload.py:24-42; dada/payload.py:13-14)
     for (int n = 0; n < 16; ++n)  h_levels[BB_CODER_INT][2][n] = (float)(n < 8 ? n : n - 16);
     for (int n = 0; n < 256; ++n) h_levels[BB_CODER_INT][3][n] = (float)(int8_t)(uint8_t)n;
+    for (int c = 0; c < 3; ++c)
+        for (int lb = 0; lb < 4; ++lb)
+            for (int n = 0; n < 256; ++n) {
+                h_levels16[0][c][lb][n] = bb_f32_to_f16(h_levels[c][lb][n]);
+                h_levels16[1][c][lb][n] = bb_f32_to_bf16(h_levels[c][lb][n]);
+            }
 }
 
 inline int log2_bps(int bps)
@@ -134,6 +145,7 @@ int ensure_init()
     std::lock_guard<std::mutex> lock(g_init_mutex);
     std::call_once(h_levels_once, fill_host_levels);
     BB_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_levels), h_levels, sizeof(h_levels)));
+    BB_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_levels16), h_levels16, sizeof(h_levels16)));
     BB_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_enc2_thr), h_enc2_thr, sizeof(h_enc2_thr)));
     if (dev < 64) g_dev_inited.fetch_or(1ull << dev, std::memory_order_release);
     return BB_OK;
@@ -144,6 +156,14 @@ int device_levels(int coder, int lb, const float **p)
     float *base = nullptr;
     BB_HIP(hipGetSymbolAddress((void **)&base, HIP_SYMBOL(g_levels)));
     *p = base + ((size_t)coder * 4 + lb) * 256;
+    return BB_OK;
+}
+
+int device_levels16(int out_type, int coder, int lb, const uint16_t **p)
+{
+    uint16_t *base = nullptr;
+    BB_HIP(hipGetSymbolAddress((void **)&base, HIP_SYMBOL(g_levels16)));
+    *p = base + (((size_t)(out_type - 1) * 3 + coder) * 4 + lb) * 256;
     return BB_OK;
 }
 
@@ -495,6 +515,135 @@ void launch_flat_lut(int bps, bool nt, dim3 grid, hipStream_t st, const bb_flat_
     });
 }
 
+// ---- 16-bit output (k_half.h) ------------------------------------------------
+// more thread slots than this do not fit the interleave kernel's staging (8 bytes of
+// offset and at least 8 bytes of payload per slot in LDS)
+#define BB_HALF_MAX_SLOTS 2048
+
+// The parameter checks of bb_decode_frames that need neither buffers nor a device,
+// shared with bb_decode_out_check.
+int decode_params_check(const bb_decode_params *p)
+{
+    if (!p) return BB_EINVAL;
+    if (p->out_type != BB_OUT_F32 && p->out_type != BB_OUT_F16 && p->out_type != BB_OUT_BF16) return BB_EINVAL;
+    if (!coder_supported(p->coder, p->bps)) return BB_ENOTSUP;
+    if (p->nslot < 1 || p->chunk < 1) return BB_EINVAL;
+    if (p->payload_nbytes == 0 || (p->payload_nbytes & 3)) return BB_EINVAL;
+    if (p->nslot > 1) {
+        if (p->chunk & (p->chunk - 1)) return BB_ENOTSUP;   // VDIF nchan is 2^k
+        if ((p->payload_nbytes * 8 / (uint64_t)p->bps) % (uint64_t)p->chunk) return BB_EINVAL;
+        if (p->out_type != BB_OUT_F32 && p->nslot > BB_HALF_MAX_SLOTS) return BB_ENOTSUP;
+    }
+    return BB_OK;
+}
+
+inline uint16_t half_pattern(int out_type, float x)
+{
+    return out_type == BB_OUT_F16 ? bb_f32_to_f16(x) : bb_f32_to_bf16(x);
+}
+
+template <class K>
+inline void launch_half(int bps, K &&k)
+{
+    using std::integral_constant;
+    switch (bps) {
+        case 1: k(integral_constant<int, 1>{}); break;
+        case 2: k(integral_constant<int, 2>{}); break;
+        case 4: k(integral_constant<int, 4>{}); break;
+        default: k(integral_constant<int, 8>{}); break;
+    }
+}
+
+// bb_decode_frames for out_type BB_OUT_F16 / BB_OUT_BF16: the same argument rules, `d_out`
+// counts 16-bit elements.
+int decode_half(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size_t nframes,
+                const bb_decode_params *p, void *d_out, size_t out_elems, void *stream)
+{
+    int rc = decode_params_check(p);
+    if (rc) return rc;
+    if (nframes == 0) return BB_OK;
+    if (!d_buf || !d_out) return BB_EINVAL;
+    if (((uintptr_t)d_buf & 3) || ((uintptr_t)d_out & 15)) return BB_EINVAL;
+    const uint64_t E = p->payload_nbytes * 8 / (uint64_t)p->bps;
+    const uint64_t nfs = (uint64_t)nframes * (uint64_t)p->nslot;
+    if (out_elems < nfs * E) return BB_ERANGE;
+    if (!d_src) {
+        if ((p->src0 & 3) || (p->src_stride & 3) || p->src0 < 0 || p->src_stride < 0) return BB_EINVAL;
+        if ((uint64_t)p->src0 + (nfs - 1) * (uint64_t)p->src_stride + p->payload_nbytes > buf_nbytes)
+            return BB_ERANGE;
+    }
+    rc = ensure_init();
+    if (rc) return rc;
+    bb_half_args a;
+    a.buf = (const uint8_t *)d_buf;
+    a.src = d_src;
+    a.out = (uint16_t *)d_out;
+    rc = device_levels16(p->out_type, p->coder, log2_bps(p->bps), &a.tab);
+    if (rc) return rc;
+    a.nfs = nfs;
+    a.ndw = p->payload_nbytes / 4;
+    a.nseg = 1; a.seg_tiles = 0; a.tpw = 0; a.seg_bytes = 0;
+    a.nslot = (uint32_t)p->nslot;
+    a.chunk = (uint32_t)p->chunk;
+    a.lchunk = 0;
+    while ((1u << a.lchunk) < a.chunk) ++a.lchunk;
+    const uint16_t fre = half_pattern(p->out_type, p->fill_re);
+    const uint16_t fim = p->complex_data ? half_pattern(p->out_type, p->fill_im) : fre;
+    a.fill = (uint32_t)fre | ((uint32_t)fim << 16);
+    a.src0 = p->src0;
+    a.src_stride = p->src_stride;
+    a.src_lim = src_limit(buf_nbytes, p->payload_nbytes);
+    hipStream_t st = (hipStream_t)stream;
+    const uint64_t out_bytes = nfs * E * 2;
+    const int tb = g_tune_blocks.load();
+    const char *tname = p->out_type == BB_OUT_F16 ? "f16" : "bf16";
+
+    if (p->nslot == 1) {
+        // contiguous output: 2 waves x up to 8 tiles per work item.  Default 8 tiles per wave
+        // (4 for 1-bit samples): a work item then writes 32 KiB for 1- and 2-bit samples,
+        // the size rounds 2-4 found best for the float32 kernels (a 16-bit item writes half
+        // the bytes of a float32 one for the same input); BB_TUNE_LUT_TILES overrides.
+        const uint64_t ntiles = (a.ndw + 63) / 64;
+        int tiles = g_tune_lut_tpw.load();
+        if (tiles == 0) tiles = p->bps == 1 ? 4 : 8;
+        tiles = tiles < 1 ? 1 : tiles > 8 ? 8 : tiles;
+        const uint64_t seg_max = 2ull * (uint64_t)tiles;
+        a.nseg = (ntiles + seg_max - 1) / seg_max;
+        a.seg_tiles = (uint32_t)((ntiles + a.nseg - 1) / a.nseg);
+        a.tpw = (a.seg_tiles + 1) / 2;
+        uint64_t b2 = nfs * a.nseg;
+        a.perm = make_perm(b2, out_bytes, BB_ORDER_FLAT);
+        const uint64_t cap = tb > 0 ? (uint64_t)tb : (1ull << 23);
+        if (b2 > cap) b2 = cap;
+        const dim3 g2((unsigned)b2);
+        launch_half(p->bps, [&](auto B) {
+            hipLaunchKernelGGL((k_decode_half_flat<decltype(B)::value, 2, 8>), g2, dim3(2 * BB_WAVE), 0, st, a);
+        });
+        BB_NOTE("k_decode_half_flat<%d,2,8> %s grid %u tiles/wave %u", p->bps, tname, g2.x, a.tpw);
+        BB_HIP(hipGetLastError());
+        return BB_OK;
+    }
+
+    // thread interleave: a work item stages the same `seg_bytes` of every slot's payload,
+    // 16 KiB in all (a power of two, so that items start on row boundaries or inside one row)
+    uint32_t sb = 8;
+    while (sb < 4096 && (uint64_t)sb * 2 * (uint64_t)p->nslot <= 16384) sb *= 2;
+    a.seg_bytes = sb;
+    a.nseg = (p->payload_nbytes + sb - 1) / sb;
+    uint64_t gb = (uint64_t)nframes * a.nseg;
+    a.perm = make_perm(gb, out_bytes, BB_ORDER_GATHER);
+    const uint64_t gcap = tb > 0 ? (uint64_t)tb : BB_GRID_CAP;
+    if (gb > gcap) gb = gcap;
+    const dim3 gg((unsigned)gb);
+    const size_t lds = (size_t)p->nslot * (8 + (size_t)sb);
+    launch_half(p->bps, [&](auto B) {
+        hipLaunchKernelGGL((k_decode_half_rows<decltype(B)::value>), gg, dim3(BB_BLOCK), lds, st, a);
+    });
+    BB_NOTE("k_decode_half_rows<%d> %s grid %u bytes/slot %u lds %zu", p->bps, tname, gg.x, sb, lds);
+    BB_HIP(hipGetLastError());
+    return BB_OK;
+}
+
 #if BB_EXP
 #include "bb_exp.inc"
 #endif
@@ -532,6 +681,20 @@ int bb_get_levels(int coder, int bps, float *h_out, size_t n)
     memcpy(h_out, h_levels[coder][log2_bps(bps)], sizeof(float) << bps);
     return BB_OK;
 }
+
+int bb_get_levels_as(int coder, int bps, int out_type, void *h_out, size_t n)
+{
+    if (out_type == BB_OUT_F32) return bb_get_levels(coder, bps, (float *)h_out, n);
+    if (out_type != BB_OUT_F16 && out_type != BB_OUT_BF16) return BB_EINVAL;
+    if (!h_out) return BB_EINVAL;
+    if (!coder_supported(coder, bps)) return BB_ENOTSUP;
+    if (n < ((size_t)1 << bps)) return BB_ERANGE;
+    std::call_once(h_levels_once, fill_host_levels);
+    memcpy(h_out, h_levels16[out_type - 1][coder][log2_bps(bps)], sizeof(uint16_t) << bps);
+    return BB_OK;
+}
+
+int bb_decode_out_check(const bb_decode_params *p) { return decode_params_check(p); }
 
 int bb_get_encode_thresholds(float h_thr[3])
 {
@@ -801,6 +964,8 @@ int bb_decode_frames(const void *d_buf, size_t buf_nbytes,
                      float *d_out, size_t out_elems, void *stream)
 {
     if (!p) return BB_EINVAL;
+    if (p->out_type != BB_OUT_F32)          // 16-bit output (or an unknown type: BB_EINVAL)
+        return decode_half(d_buf, buf_nbytes, d_src, nframes, p, d_out, out_elems, stream);
     if (!coder_supported(p->coder, p->bps)) return BB_ENOTSUP;
     if (nframes == 0) return BB_OK;
     if (!d_buf || !d_out) return BB_EINVAL;
@@ -1145,6 +1310,8 @@ struct select_geom { uint32_t lchunk, gt; uint64_t R, ntiles; size_t lds; };
 static int select_geometry(const bb_decode_params *p, int nwithin, select_geom *g)
 {
     if (!p) return BB_EINVAL;
+    if (p->out_type != BB_OUT_F32)          // channel subsets are decoded to float32 only
+        return (p->out_type == BB_OUT_F16 || p->out_type == BB_OUT_BF16) ? BB_ENOTSUP : BB_EINVAL;
     if (!coder_supported(p->coder, p->bps)) return BB_ENOTSUP;
     if (p->nslot < 1 || p->chunk < 1 || nwithin < 1 || nwithin > 4096) return BB_EINVAL;
     if (p->payload_nbytes == 0 || (p->payload_nbytes & 3)) return BB_EINVAL;
@@ -1194,6 +1361,16 @@ int bb_touch(const void *d_buf, size_t nbytes, void *stream)
 // boxes, within +-1 % at 2^16 (too large: not read) and below 16 MiB (profiles/r06cx_, r06cy_exp_touch_read.log;
 // with NONTEMPORAL loads in the pre-read the reads got 2.4-3.8 % slower: those go past the
 // cache, r06cw_).
+// a window asked for 16-bit output is refused BEFORE its scan is launched when the decode
+// would not take it (an unknown type, or a channel subset: float32 only)
+static int window_out_check(const bb_decode_params *dec, int nwithin)
+{
+    if (dec->out_type == BB_OUT_F32) return BB_OK;
+    const int rc = decode_params_check(dec);
+    if (rc != BB_OK) return rc;
+    return nwithin > 0 ? BB_ENOTSUP : BB_OK;
+}
+
 static int touch_window(const void *d_buf, size_t nbytes, void *stream)
 {
     const uint64_t lim = (uint64_t)g_tune_touch_mib.load() << 20;
@@ -1213,6 +1390,7 @@ int bb_vdif_read_window(const void *d_buf, size_t nbytes,
 {
     if (!scan || !dec || !d_src || dec->nslot < 1) return BB_EINVAL;
     if (scan_stream && !verified) return BB_EINVAL;        // (the decode's stream waits for that event)
+    { const int orc = window_out_check(dec, nwithin); if (orc != BB_OK) return orc; }
     void *ss = scan_stream ? scan_stream : stream;
     { const int trc = touch_window(d_buf, nbytes, stream); if (trc != BB_OK) return trc; }
     // three launches: scan (which also pre-sets the index to -1), index + verification, decode
@@ -1240,6 +1418,7 @@ int bb_mark5b_read_window(const void *d_buf, size_t nbytes,
 {
     if (!scan || !dec) return BB_EINVAL;
     if (scan_stream && !verified) return BB_EINVAL;
+    { const int orc = window_out_check(dec, nwithin); if (orc != BB_OK) return orc; }
     void *ss = scan_stream ? scan_stream : stream;
     { const int trc = touch_window(d_buf, nbytes, stream); if (trc != BB_OK) return trc; }
     int rc = bb_mark5b_scan(d_buf, nbytes, scan, d_recs, nframes, ss);
@@ -1651,6 +1830,8 @@ static int m4_check(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, 
                     const bb_mark4_decode_params *p, int nout, const float *d_out, size_t out_elems,
                     unsigned out_align)
 {
+    if (p->out_type != BB_OUT_F32)          // the Mark 4 kernels write float32 only
+        return (p->out_type == BB_OUT_F16 || p->out_type == BB_OUT_BF16) ? BB_ENOTSUP : BB_EINVAL;
     if (!d_buf || !d_out) return BB_EINVAL;
     if (p->nwords == 0 || p->fill_words > p->nwords) return BB_EINVAL;
     if (((uintptr_t)d_buf & 7) || ((uintptr_t)d_out & (out_align - 1))) return BB_EINVAL;

@@ -184,6 +184,10 @@ class DADAStreamReader(BlockStreamReader):
             self._flat_rows(dbuf, 1, 0, (b - a) * rb, 0, out_flat)
         return pieces, decode
 
+    def _half_geometry(self):
+        # plain int8 samples go through bb_decode_frames, `n` bytes per frame (any multiple of 4)
+        return (_lib.CODER_INT, 8, 1, 1, 4) if self.bps == 8 and not self._mkbf else None
+
     def _flat_rows(self, dbuf, nframes, lo, n, stride, out_flat):
         """`n` bytes of whole samples from each of `nframes` frames, at ``lo +
         i * stride`` -> float32 values in `out_flat`; with a planned channel
@@ -196,7 +200,8 @@ class DADAStreamReader(BlockStreamReader):
             try:
                 kernels.decode_frames(dbuf, nframes, n, _lib.CODER_INT, 8,
                                       chunk=rb if within is not None else 1, src0=lo,
-                                      src_stride=stride, out=out_flat, within=within)
+                                      src_stride=stride, out=out_flat, within=within,
+                                      out_dtype=out_flat.dtype)
                 return
             except (KeyError, _lib.BBError):
                 if within is None:

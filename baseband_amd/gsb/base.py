@@ -252,6 +252,10 @@ class GSBStreamReader(GPUStreamReaderBase):
     def _set_nbytes(self):
         return self._payload_nbytes * len(self._images) * self._nfiles
 
+    def _half_geometry(self):
+        chunk = self._unsliced_shape[-1] * (2 if self.complex_data else 1)
+        return (_lib.CODER_INT, self.bps, chunk, 1 if self._rawdump else len(self._images), self._payload_nbytes)
+
     def _process_window(self, dbuf, first, last, out_flat):
         """Decode sets [first, last) staged in `dbuf` ([set][pol][part][block])."""
         nsets = last - first
@@ -262,7 +266,7 @@ class GSBStreamReader(GPUStreamReaderBase):
         chunk = nchan * (2 if self.complex_data else 1)
         if self._rawdump:
             kernels.decode_frames(dbuf, nsets, pn, _lib.CODER_INT, self.bps,
-                                  chunk=chunk, src0=0, src_stride=pn, out=out_flat)
+                                  chunk=chunk, src0=0, src_stride=pn, out=out_flat, out_dtype=out_flat.dtype)
             return
         # output frame (k, part f), slot = polarisation p
         k = torch.arange(nsets, device=dbuf.device, dtype=torch.int64)[:, None, None]
@@ -271,7 +275,8 @@ class GSBStreamReader(GPUStreamReaderBase):
         dsrc = (((k * npol + p) * F + f) * pn).reshape(-1).contiguous()
         kernels.decode_frames(dbuf, nsets * F, pn, _lib.CODER_INT, self.bps,
                               chunk=chunk, nslot=npol, src=dsrc,
-                              complex_data=self.complex_data, out=out_flat, within=self._within)
+                              complex_data=self.complex_data, out=out_flat, within=self._within,
+                              out_dtype=out_flat.dtype)
 
 
 class _BlockSetImage:
@@ -461,7 +466,15 @@ def open(name, mode='rs', **kwargs):
             raw = (raw,)
         fh_raw = tuple(tuple(handle(f) for f in pair) for pair in raw)
     if rw == 'r':
+        sample_dtype = kwargs.pop('sample_dtype', None)     # (a reader attribute, base/opener.py)
         reader = GSBStreamReader(fh_ts, fh_raw, **kwargs)
+        if sample_dtype is not None:
+            try:
+                reader.sample_dtype = sample_dtype
+            except Exception:
+                reader.close()
+                raise
+            kwargs = dict(kwargs, sample_dtype=sample_dtype)
         # pickling / copying: the files are opened again by name on arrival
         source = (_name_of(fh_ts), _name_of(fh_raw))
         if source[0] is not None and source[1] is not None:

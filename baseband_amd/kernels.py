@@ -90,11 +90,37 @@ def to_device_bytes(raw, device=None):
     return torch.from_numpy(np.array(a, copy=True)).to(device or 'cuda')
 
 
-def _empty_output(nelem, device):
-    """float32 output tensor of a decode launch: from the placement arena when
-    there is one (placement.empty_output), else torch.empty."""
+def _empty_output(nelem, device=None, dtype=torch.float32):
+    """Flat output tensor of a decode launch (float32, or float16 / bfloat16 for
+    a 16-bit decode): from the placement arena when there is one
+    (placement.empty_output), else torch.empty.  The arena hands out float32
+    blocks: 16-bit outputs are views of one, so that they are placed like the
+    float32 results they replace."""
     from .placement import empty_output
-    return empty_output(nelem, torch.float32, device)
+    if dtype in (torch.float16, torch.bfloat16):
+        return empty_output((int(nelem) + 1) // 2, torch.float32, device).view(dtype)[:int(nelem)]
+    return empty_output(nelem, dtype, device)
+
+
+empty_decoded = _empty_output
+
+
+def _out_type(dtype):
+    """torch element type of a decode's output -> enum bb_out_type."""
+    t = _lib.out_type_of(dtype)
+    if t is None or dtype.is_complex:
+        raise TypeError("decoded samples are float32, float16 or bfloat16 elements, not {}".format(dtype))
+    return t
+
+
+def out_supported(coder, bps, chunk, nslot, payload_nbytes, dtype):
+    """Would `decode_frames(..., out_dtype=dtype)` take these parameters?  Asks the
+    library (bb_decode_out_check; no device needed); readers plan a 16-bit decode
+    with it and keep float32-then-convert where it says no."""
+    p = _lib.DecodeParams()
+    p.coder, p.bps, p.chunk, p.nslot, p.payload_nbytes = coder, bps, chunk, nslot, payload_nbytes
+    p.out_type = _out_type(dtype)
+    return lib.bb_decode_out_check(C.byref(p)) == _lib.BB_OK
 
 
 class _Target:
@@ -104,12 +130,14 @@ class _Target:
     decoded into a temporary and copied into place afterwards."""
     __slots__ = ('want', 'use')
 
-    def __init__(self, out, nelem, device):
+    def __init__(self, out, nelem, device, dtype=torch.float32):
         self.want = out
         if out is None:
-            self.use = _empty_output(nelem, device)
+            self.use = _empty_output(nelem, device, dtype)
+        elif out.dtype != dtype:
+            raise TypeError("output tensor is {}, the decode writes {}".format(out.dtype, dtype))
         elif out.data_ptr() % 16 or not out.is_contiguous():
-            self.use = _empty_output(out.numel(), device)
+            self.use = _empty_output(out.numel(), device, dtype)
         else:
             self.use = out
 
@@ -248,7 +276,8 @@ class VDIFWindow(_FrameWindow):
     def run(self, dbuf, ref_frame_nr, nframes, thread_slot, nsets, within, out,
             recs_per_index, nstrict, nbad, verified, scan_stream=None):
         """Launch the window on torch's current stream.  `out`: flat float32
-        device tensor; `nbad`: int32[1] device counter, or None for no
+        (or, without `within`, float16 / bfloat16: the decode then writes that
+        type, bb_decode_params.out_type) device tensor; `nbad`: int32[1] device counter, or None for no
         verification; `verified`: raw handle of the event to record behind the
         verification launch, or None; `scan_stream`: torch stream for the scan /
         index / verification launches (needs `verified`; `_FrameWindow`)."""
@@ -257,7 +286,8 @@ class VDIFWindow(_FrameWindow):
         if not verified:
             scan_stream = None
         st = self._scratch(nframes, nsets * self.dec.nslot, dev, scan_stream)
-        tgt = _Target(out, out.numel(), dev)
+        self.dec.out_type = _out_type(out.dtype)
+        tgt = _Target(out, out.numel(), dev, out.dtype)
         nsel = within.numel() if within is not None else 0
         check(lib.bb_vdif_read_window(
             _ptr(dbuf), dbuf.numel(), C.byref(self.scan), nframes, _ptr(thread_slot), nsets,
@@ -293,7 +323,8 @@ class Mark5BWindow(_FrameWindow):
         if not verified:
             scan_stream = None
         st = self._scratch(nframes, n, dbuf.device, scan_stream)
-        tgt = _Target(out, out.numel(), dbuf.device)
+        self.dec.out_type = _out_type(out.dtype)
+        tgt = _Target(out, out.numel(), dbuf.device, out.dtype)
         check(lib.bb_mark5b_read_window(
             _ptr(dbuf), dbuf.numel(), C.byref(self.scan), nframes, n, C.byref(self.dec), _ptr(within),
             within.numel() if within is not None else 0, _ptr(self.recs), _ptr(self.src), _ptr(tgt.use),
@@ -480,12 +511,15 @@ def build_index(recs, nframes_out, nslot=1, thread_slot=None):
 
 def decode_frames(dbuf, nframes, payload_nbytes, coder, bps, chunk=1, nslot=1,
                   src=None, src0=0, src_stride=0, complex_data=False,
-                  fill_value=0., out=None, within=None):
+                  fill_value=0., out=None, within=None, out_dtype=torch.float32):
     """Decode `nframes` frame(set)s to a flat float32 device tensor.  `within`
     (int32 device tensor of positions inside a thread sample's `chunk`
     floats) selects channels in the kernel: only those positions are
-    written (bb_decode_frames_select)."""
+    written (bb_decode_frames_select).  `out_dtype` torch.float16 /
+    torch.bfloat16: the kernels write that type (the float32 value rounded to
+    nearest even; k_half.h); KeyError with `within`."""
     p = _lib.DecodeParams()
+    p.out_type = _out_type(out_dtype)
     p.coder = coder
     p.bps = bps
     p.chunk = chunk
@@ -504,12 +538,12 @@ def decode_frames(dbuf, nframes, payload_nbytes, coder, bps, chunk=1, nslot=1,
         nsel = within.numel()
         nelem = nelem // chunk * nsel
         if out is None:
-            out = _empty_output(nelem, dbuf.device)
+            out = _empty_output(nelem, dbuf.device, out_dtype)
         check(lib.bb_decode_frames_select(_ptr(dbuf), dbuf.numel(), _ptr(src), nframes, C.byref(p),
                                           _ptr(within), nsel, _ptr(out), out.numel(), _stream(dbuf)),
               'bb_decode_frames_select')
         return out
-    tgt = _Target(out, nelem, dbuf.device)
+    tgt = _Target(out, nelem, dbuf.device, out_dtype)
     check(lib.bb_decode_frames(_ptr(dbuf), dbuf.numel(), _ptr(src), nframes,
                                C.byref(p), _ptr(tgt.use), tgt.use.numel(), _stream(dbuf)),
           'bb_decode_frames')
@@ -590,13 +624,16 @@ def mark4_select_maps(sign_bit, mag_bit, nchan, channels):
 
 
 def decode_mark4(dbuf, nframes, ntrack, nwords, sign_bit, mag_bit, fill_words=0,
-                 src=None, src0=0, src_stride=0, fill_value=0., out=None, select=False):
+                 src=None, src0=0, src_stride=0, fill_value=0., out=None, select=False,
+                 out_dtype=torch.float32):
     """Track-demultiplex `nframes` units of `nwords` stream words each ->
     flat float32 device tensor of nframes * nwords * ntrack/2 values.  With
     `select` the maps may be shorter (the outputs of the channels a reader's
     subset keeps, `mark4_select_maps`): every word then gives ``len(sign_bit)``
-    values (bb_decode_mark4_select)."""
+    values (bb_decode_mark4_select).  The Mark 4 kernels write float32 only:
+    KeyError (BB_ENOTSUP) for any other `out_dtype`, nothing is launched."""
     p = _lib.Mark4DecodeParams()
+    p.out_type = _out_type(out_dtype)
     p.ntrack = ntrack
     p.nwords = nwords
     p.fill_words = fill_words
@@ -610,12 +647,12 @@ def decode_mark4(dbuf, nframes, ntrack, nwords, sign_bit, mag_bit, fill_words=0,
         nout = len(sign_bit)
         nelem = nframes * nwords * nout
         if out is None:
-            out = _empty_output(nelem, dbuf.device)
+            out = _empty_output(nelem, dbuf.device, out_dtype)
         check(lib.bb_decode_mark4_select(_ptr(dbuf), dbuf.numel(), _ptr(src), nframes, C.byref(p),
                                          nout, _ptr(out), out.numel(), _stream(dbuf)),
               'bb_decode_mark4_select')
         return out
-    tgt = _Target(out, nframes * nwords * (ntrack // 2), dbuf.device)
+    tgt = _Target(out, nframes * nwords * (ntrack // 2), dbuf.device, out_dtype)
     check(lib.bb_decode_mark4(_ptr(dbuf), dbuf.numel(), _ptr(src), nframes,
                               C.byref(p), _ptr(tgt.use), tgt.use.numel(), _stream(dbuf)),
           'bb_decode_mark4')
@@ -624,7 +661,7 @@ def decode_mark4(dbuf, nframes, ntrack, nwords, sign_bit, mag_bit, fill_words=0,
 
 def decode_i8_tiled(dbuf, nframes, layout, npol, nchan, ntime, t_lo, t_hi,
                     src=None, src0=0, src_stride=0, fill_value=0., out=None, nchan_stored=0,
-                    npol_stored=0, pol_first=0, chan_map=None):
+                    npol_stored=0, pol_first=0, chan_map=None, out_dtype=torch.float32):
     """int8 (re, im) -> complex64 with the (time, pol, chan) permutation of
     `layout`; rows [t_lo, t_hi) of every frame -> flat float32 tensor.  With
     `nchan_stored` the payload holds that many channels and the `nchan`
@@ -632,7 +669,11 @@ def decode_i8_tiled(dbuf, nframes, layout, npol, nchan, ntime, t_lo, t_hi,
     SELECTION -- `chan_map` (int32 device tensor of `nchan` stored-channel
     numbers) and / or `npol` of `npol_stored` polarisations from `pol_first` on
     -- is decoded from payload offsets that point at the payload start;
-    KeyError when the library's fast form does not take the geometry."""
+    KeyError when the library's fast form does not take the geometry -- and for
+    an `out_dtype` other than float32: bb_tiled_params has no output type, the
+    transposing kernels write float32 only (BB_ENOTSUP without a call)."""
+    if _out_type(out_dtype) != _lib.OUT_F32:
+        check(_lib.BB_ENOTSUP, 'bb_decode_i8_tiled')
     p = _lib.TiledParams()
     p.layout = layout
     p.npol = npol

@@ -275,9 +275,10 @@ class Mark4StreamReader(GPUStreamReaderBase):
         return kernels.mark4_select_maps(sign, mag, self._unsliced_shape[0],
                                          self._within_np) + (True,)
 
-    def _read_sets(self, first, last, into=None):
+    def _decode_sets(self, first, last, into, elem):
+        # (float32 only: no `_half_geometry`, `_read_sets` converts for 16-bit results)
         if self._resident is None:
-            return super()._read_sets(first, last, into)
+            return super()._decode_sets(first, last, into, elem)
         dev, src = self._resident
         self._warn_damage(first, last)
         sign, mag, select = self._maps()

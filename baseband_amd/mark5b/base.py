@@ -204,16 +204,19 @@ class Mark5BStreamReader(GPUStreamReaderBase):
         self._relocated = True
         self._note_damage(self._resident[1])
 
-    def _read_sets(self, first, last, into=None):
+    def _half_geometry(self):
+        return (_lib.CODER_MARK5B, self.bps, self._unsliced_shape[0], 1, 10000)
+
+    def _decode_sets(self, first, last, into, elem):
         if self._resident is None:
-            return super()._read_sets(first, last, into)
+            return super()._decode_sets(first, last, into, elem)
         dev, src = self._resident
         self._warn_damage(first, last)
         flat = kernels.decode_frames(
             dev, last - first, 10000, _lib.CODER_MARK5B, self.bps,
             chunk=self._unsliced_shape[0], nslot=1,
             src=src[first:last].contiguous(), fill_value=self.fill_value, out=into,
-            within=self._within)
+            within=self._within, out_dtype=elem)
         return flat.reshape(((last - first) * self.samples_per_frame,)
                             + tuple(self._decode_shape))
 

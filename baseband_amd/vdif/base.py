@@ -532,9 +532,14 @@ class VDIFStreamReader(GPUStreamReaderBase):
     def _slip_message(self, k, nbytes):
         return "problem loading frame set {}. Stream off by {} bytes.".format(k, nbytes)
 
-    def _read_sets(self, first, last, into=None):
+    def _half_geometry(self):
+        h0 = self.header0
+        return (self._coder, self.bps, h0.nchan * (2 if self.complex_data else 1), len(self._thread_ids),
+                h0.payload_nbytes)
+
+    def _decode_sets(self, first, last, into, elem):
         if self._resident is None:
-            return super()._read_sets(first, last, into)
+            return super()._decode_sets(first, last, into, elem)
         dev, src = self._resident
         if self.verify is True:         # (strict: every read answers for the sets it covers)
             err = self._strict_error(self._first_problem_met(first, last),
@@ -550,7 +555,7 @@ class VDIFStreamReader(GPUStreamReaderBase):
             dev, nsets, h0.payload_nbytes, self._coder, self.bps, chunk=chunk,
             nslot=nslot, src=src[first * nslot:last * nslot].contiguous(),
             complex_data=self.complex_data, fill_value=self.fill_value, out=into,
-            within=self._within)
+            within=self._within, out_dtype=elem)
         if self.complex_data:
             flat = torch.view_as_complex(flat.view(-1, 2))
         return flat.reshape((nsets * self.samples_per_frame,) + tuple(self._decode_shape))

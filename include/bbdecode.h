@@ -30,6 +30,9 @@
  *    (the reference surfaces an unknown coder as KeyError from the _decoders
  *    dict, base/payload.py:314-315).
  *  - decoded output is float32; complex64 is (re, im) interleaved float32.
+ *    bb_decode_frames and the VDIF / Mark 5B window calls can instead write
+ *    float16 or bfloat16 elements (bb_decode_params.out_type): the float32
+ *    value rounded once to nearest even, (re, im) interleaved likewise.
  */
 #ifndef BBDECODE_H
 #define BBDECODE_H
@@ -41,7 +44,7 @@
 extern "C" {
 #endif
 
-#define BB_ABI_VERSION 7   /* 7 (round 6): bb_touch; the *_read_window calls read small windows through first */   /* 6 (round 6): bb_mark5b_locate_stream */   /* 5 (round 6): bb_arena_stats grew (first_probe_gbps .. second_chance_wins) */   /* 4 (round 5): bb_arena_prepare, bb_arena_owns, bb_arena_stats grew (va_ranges .. prepare_wait_ms); the `reserved` words of the scan parameter blocks got meanings whose zero is the old behaviour (bb_vdif_scan_params.set_nframes, bb_mark5b_/bb_mark4_scan_params.by_position): same layout  */   /* 3 (round 4): bb_copy_frames; bb_arena_stats grew va_reserved / va_used; bb_tune knobs are thread-local */   /* 2: bb_tiled_params grew (npol_stored, pol_first, d_chan_map) */
+#define BB_ABI_VERSION 7   /* 7, additive: bb_decode_params.reserved became out_type (zero = float32, the old behaviour; same layout), bb_mark4_decode_params.reserved likewise (float32 only), bb_decode_out_check, bb_get_levels_as */   /* 7 (round 6): bb_touch; the *_read_window calls read small windows through first */   /* 6 (round 6): bb_mark5b_locate_stream */   /* 5 (round 6): bb_arena_stats grew (first_probe_gbps .. second_chance_wins) */   /* 4 (round 5): bb_arena_prepare, bb_arena_owns, bb_arena_stats grew (va_ranges .. prepare_wait_ms); the `reserved` words of the scan parameter blocks got meanings whose zero is the old behaviour (bb_vdif_scan_params.set_nframes, bb_mark5b_/bb_mark4_scan_params.by_position): same layout  */   /* 3 (round 4): bb_copy_frames; bb_arena_stats grew va_reserved / va_used; bb_tune knobs are thread-local */   /* 2: bb_tiled_params grew (npol_stored, pol_first, d_chan_map) */
 
 /* error codes (negative errno values) */
 #define BB_OK        0
@@ -69,6 +72,20 @@ enum bb_coder {
     BB_CODER_VDIF   = 0,
     BB_CODER_MARK5B = 1,
     BB_CODER_INT    = 2
+};
+
+/*
+ * Element type of decoded output (bb_decode_params.out_type).  The 16-bit types
+ * hold the float32 value the reference produces (base/payload.py:314-330 with the
+ * tables of vdif/payload.py:25-103, mark5b/payload.py:27-94, base/encoding.py:
+ * 131-144) rounded once to nearest even: every sample value of the 1-, 2-, 4-bit
+ * and int8 coders is a table entry, so the library converts the tables (and the
+ * fill value) once on the host and the kernels move 16-bit patterns.
+ */
+enum bb_out_type {
+    BB_OUT_F32  = 0,    /* float32 (the default: the word was `reserved`, zero) */
+    BB_OUT_F16  = 1,    /* IEEE binary16 */
+    BB_OUT_BF16 = 2     /* bfloat16 */
 };
 
 /* flags in bb_frame_rec.flags */
@@ -110,6 +127,13 @@ int         bb_init(void);
 /* Copy the 2^bps-entry code -> level table of (coder, bps) to host memory
  * (what vdif/payload.py:25-63 and mark5b/payload.py:27-72 tabulate per byte). */
 int         bb_get_levels(int coder, int bps, float *h_levels, size_t n);
+/* The same table in an output type (enum bb_out_type): 2^bps uint16 bit patterns
+ * for BB_OUT_F16 / BB_OUT_BF16, float32 for BB_OUT_F32 (then bb_get_levels).  The
+ * single place where the 16-bit types are rounded (nearest even, on the host);
+ * stands for the tables of vdif/payload.py:25-103, mark5b/payload.py:27-94 and
+ * decode_8bit (base/encoding.py:131-144) followed by ndarray.astype.  No device
+ * needed.  BB_EINVAL for an unknown type. */
+int         bb_get_levels_as(int coder, int bps, int out_type, void *h_levels, size_t n);
 /* The three float32 inputs at which the 2-bit encoder (encode_2bit_base,
  * base/encoding.py:77-102) steps to code 1, 2, 3: code(x) = #{k : x >= thr[k]}.
  * Found on the host by bisection over the reference arithmetic. */
@@ -295,13 +319,30 @@ typedef struct bb_decode_params {
     int32_t  complex_data;     /* selects (fill_re, fill_im) vs fill_re only */
     float    fill_re;
     float    fill_im;
-    int32_t  reserved;
+    int32_t  out_type;         /* enum bb_out_type; 0 = float32.  With BB_OUT_F16 / BB_OUT_BF16
+                                * d_out is REINTERPRETED: it points to out_elems 16-bit elements
+                                * (out_elems keeps counting elements; 16-byte alignment as for
+                                * float32), the fill value is rounded like the levels.  Honoured by
+                                * bb_decode_frames, bb_vdif_read_window and bb_mark5b_read_window;
+                                * bb_decode_frames_select (and a window call with nwithin > 0)
+                                * answers BB_ENOTSUP, nothing is launched.  Anything else: BB_EINVAL. */
 } bb_decode_params;
 
 int bb_decode_frames(const void *d_buf, size_t buf_nbytes,
                      const int64_t *d_src, size_t nframes,
                      const bb_decode_params *params,
                      float *d_out, size_t out_elems, void *stream);
+
+/*
+ * What a bb_decode_frames launch with these parameters would answer, as far as
+ * the parameters decide it (no buffers, no device): BB_OK, BB_EINVAL (unknown
+ * out_type, sizes), BB_ENOTSUP (coder / bps, a chunk that is not a power of two
+ * with nslot > 1, or a combination the 16-bit kernels do not take: more than
+ * 2048 thread slots).  Readers plan with it: where it does not say BB_OK for a
+ * 16-bit type they decode float32 and convert, which gives the same values
+ * (PayloadBase._decode followed by astype: base/payload.py:314-330).
+ */
+int bb_decode_out_check(const bb_decode_params *params);
 
 /*
  * bb_decode_frames with a CHANNEL SELECTION folded in: of every thread
@@ -472,7 +513,7 @@ int bb_mark4_scan_at(const void *d_buf, size_t nbytes,
  */
 typedef struct bb_mark4_decode_params {
     int32_t  ntrack;          /* 16, 32 or 64 */
-    int32_t  reserved;
+    int32_t  out_type;        /* enum bb_out_type; only BB_OUT_F32 (0): BB_ENOTSUP for the 16-bit types */
     uint64_t nwords;          /* stream words per unit: 20000 (frame) or payload size */
     uint64_t fill_words;      /* 160 for frames, 0 for bare payloads */
     int64_t  src0;
