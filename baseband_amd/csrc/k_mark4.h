@@ -57,8 +57,9 @@ bb_m4_load_any(const uint8_t *buf, uint64_t pos)
 // Byte-granular Mark 4 frame search: position p holds a frame
 // when stream word 63 is all zero and words 64..95 are all ones (the sync
 // pattern of every track plus the zero bit before it: mark4/header.py:345-373),
-// the whole frame fits, and -- if its pattern still fits in the buffer -- the
-// frame one later shows the same: locate_frames with check=1
+// the whole frame fits, and -- if more than the first 96 stream words of the
+// frame one later lie inside the buffer -- that frame shows the same: locate_frames
+// with check=1, whose `c < stop - offset - pattern.size` is strict
 // (mark4/base.py:110-166, base/base.py:181-335).  One lane per position; the
 // first byte (0xff) rejects nearly all of them.
 template <int NTRACK>
@@ -90,7 +91,7 @@ void k_mark4_locate(const uint8_t *buf, uint64_t nbytes, int64_t *out, uint64_t 
             if (z < ZOFF) return -1;
             const uint64_t pos = z - ZOFF;
             if (pos + FN > nbytes || !bb_m4_sync_at<NTRACK>(buf, pos)) return -1;
-            if (pos + FN + PAT_END <= nbytes && !bb_m4_sync_at<NTRACK>(buf, pos + FN)) return -1;
+            if (pos + FN + PAT_END < nbytes && !bb_m4_sync_at<NTRACK>(buf, pos + FN)) return -1;
             return (int64_t)pos;
         });
 }

@@ -87,17 +87,34 @@ void k_vdif_scan(const uint8_t *buf, uint64_t nbytes, bb_vdif_scan_params p,
     }
 }
 
+// The aligned dword at byte a of which only the bytes inside [0, nbytes) are
+// fetched (the others read as zero): the last dword of a buffer whose length
+// is not a multiple of four, byte by byte.  Header reads only, not the sweep.
+__device__ __forceinline__ uint32_t bb_load_dword_in(const uint8_t *buf, uint64_t nbytes, uint64_t a)
+{
+    if (a + 4 <= nbytes) return *reinterpret_cast<const uint32_t *>(buf + a);
+    uint32_t v = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        if (a + k < nbytes) v |= (uint32_t)buf[a + k] << (8 * k);
+    return v;
+}
+
 // Unaligned little-endian dword at byte position pos, assembled from the two
 // aligned dwords around it (positions found by the byte-granular locate
 // kernel need not be aligned once bytes went missing from a file).
+// A dword whose four bytes do not all lie inside [0, nbytes) reads as zero;
+// one that does is seen whole, also when the aligned dword that holds its top
+// bytes is cut by the end of the buffer (a file truncated inside a header
+// after a byte loss made the frames unaligned).  Nothing behind nbytes is read.
 __device__ __forceinline__ uint32_t bb_load_u32_any(const uint8_t *buf, uint64_t nbytes, uint64_t pos)
 {
+    if (pos > nbytes || pos + 4 > nbytes) return 0u;
     const uint64_t a = pos & ~3ull;
     const uint32_t sh = (uint32_t)(pos & 3) * 8;
-    const uint32_t *w = reinterpret_cast<const uint32_t *>(buf + a);
-    const uint32_t lo = (a + 4 <= nbytes) ? w[0] : 0u;
+    const uint32_t lo = *reinterpret_cast<const uint32_t *>(buf + a);
     if (sh == 0) return lo;
-    const uint32_t hi = (a + 8 <= nbytes) ? w[1] : 0u;
+    const uint32_t hi = bb_load_dword_in(buf, nbytes, a + 4);
     return (lo >> sh) | (hi << (32 - sh));
 }
 
@@ -105,7 +122,7 @@ __device__ __forceinline__ bool bb_vdif_header_at(const uint8_t *buf, uint64_t n
                                                   const bb_vdif_scan_params &p, uint64_t pos)
 {
     const int nwords = (int)(p.header_nbytes >> 2);
-    if (pos + p.header_nbytes > nbytes) return false;
+    if (pos > nbytes || pos + p.header_nbytes > nbytes) return false;
     // all nine aligned dwords that hold the (possibly unaligned) header are
     // requested before any of them is looked at: ONE memory latency per
     // header.  (Testing word by word with early exits made every true frame
@@ -115,9 +132,16 @@ __device__ __forceinline__ bool bb_vdif_header_at(const uint8_t *buf, uint64_t n
     const uint32_t sh = (uint32_t)(pos & 3) * 8;
     const uint32_t *w = reinterpret_cast<const uint32_t *>(buf + a);
     uint32_t d[9];
+    if (a + 4 * (uint64_t)nwords + 4 <= nbytes) {
 #pragma unroll
-    for (int k = 0; k < 9; ++k)
-        d[k] = (k <= nwords && a + 4 * (uint64_t)k + 4 <= nbytes) ? w[k] : 0u;
+        for (int k = 0; k < 9; ++k) d[k] = k <= nwords ? w[k] : 0u;
+    } else {
+        // the header ends in the last, cut dword of the buffer: the bytes of that
+        // dword that lie inside the buffer belong to the header and are fetched singly
+#pragma unroll
+        for (int k = 0; k < 9; ++k)
+            d[k] = k < nwords ? w[k] : (k == nwords ? bb_load_dword_in(buf, nbytes, a + 4 * (uint64_t)k) : 0u);
+    }
     bool ok = true;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -432,8 +456,8 @@ __device__ __forceinline__ bool bb_mark5b_crc_ok(uint32_t w2, uint32_t w3)
 
 // Byte-granular Mark 5B frame search: position p holds a frame
 // when the sync word sits at p, the whole frame fits in the buffer, the time
-// code passes its CRC, and -- if four more bytes fit there -- another sync word
-// sits exactly one frame later: locate_frames with check=1 plus the CRC gate
+// code passes its CRC, and -- if more than four bytes lie behind the frame -- another
+// sync word sits exactly one frame later: locate_frames with check=1 plus the CRC gate
 // of Mark5BFileReader.find_header (base/base.py:181-335, mark5b/base.py:136-155),
 // which is what the reference's _bad_frame recovery accepts
 // (base/base.py:1127-1219).  Matches are appended unordered.
@@ -449,10 +473,15 @@ void k_mark5b_locate(const uint8_t *buf, uint64_t nbytes, uint32_t w1_pattern, u
             // the user word, mark5b/header.py:70-73 -- here and one frame later, where the
             // reference's locate_frames compares the whole pattern of header0 again)
             if (w1_mask && ((bb_load_u32_any(buf, nbytes, pos + 4) ^ w1_pattern) & w1_mask)) return -1;
+            // (the pattern one frame later is looked at when MORE bytes than it is long lie behind
+            // the frame -- 4, or 8 with word 1 -- as locate_frames does: `c < stop - offset -
+            // pattern.size`, base/base.py:329-333.  A file that ends with exactly four bytes of
+            // something else behind its last frame keeps that frame.)
             const uint64_t next = pos + BB_M5B_FRAME;
-            if (next + 4 <= nbytes && bb_load_u32_any(buf, nbytes, next) != 0xABADDEEDu) return -1;
-            if (w1_mask && next + 8 <= nbytes
-                && ((bb_load_u32_any(buf, nbytes, next + 4) ^ w1_pattern) & w1_mask)) return -1;
+            if (next + (w1_mask ? 8u : 4u) < nbytes) {
+                if (bb_load_u32_any(buf, nbytes, next) != 0xABADDEEDu) return -1;
+                if (w1_mask && ((bb_load_u32_any(buf, nbytes, next + 4) ^ w1_pattern) & w1_mask)) return -1;
+            }
             if (!bb_mark5b_crc_ok(bb_load_u32_any(buf, nbytes, pos + 8),
                                   bb_load_u32_any(buf, nbytes, pos + 12))) return -1;
             return (int64_t)pos;

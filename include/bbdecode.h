@@ -167,6 +167,14 @@ typedef struct bb_vdif_scan_params {
                                * bb_vdif_read_window sets it from recs_per_index. */
 } bb_vdif_scan_params;
 
+/* Records (bb_vdif_scan and bb_vdif_scan_at): payload_offset = frame offset +
+ * header_nbytes.  A header word whose four bytes do not all lie inside the
+ * buffer reads as zero.  BB_FRAME_OK: the whole header lies inside the buffer
+ * and agrees with `pattern` under `mask`, and the whole frame fits.
+ * BB_FRAME_INVALID: the header's invalid bit.  time_index = (seconds -
+ * ref_seconds) * frame_rate + frame_nr - ref_frame_nr (the set_nframes rule
+ * applies to bb_vdif_scan only), or the frame's number in the call when
+ * frame_rate = 0; clamped to +-(2^31 - 1). */
 int bb_vdif_scan(const void *d_buf, size_t nbytes,
                  const bb_vdif_scan_params *params,
                  bb_frame_rec *d_recs, size_t nframes, void *stream);
@@ -175,9 +183,22 @@ int bb_vdif_scan(const void *d_buf, size_t nbytes,
  * Corruption-tolerant frame discovery: byte-granular
  * search for VDIF headers -- the masked-pattern search of
  * VLBIFileReaderBase.locate_frames (base/base.py:181-335) that the reference's
- * _bad_frame recovery relies on (vdif/base.py:536-755).  A position is reported
- * when the stream-invariant pattern matches, the complete frame fits, and
- * another header lies exactly one frame later (for the last frame: earlier).
+ * _bad_frame recovery relies on (vdif/base.py:536-755).  "A header stands at
+ * q" means: the header_nbytes bytes at q lie inside the buffer and agree with
+ * `pattern` under `mask`.  A position p is reported when a header stands at p,
+ * the complete frame fits (p + frame_nbytes <= nbytes), and
+ *  - if the header_nbytes bytes one frame later lie inside the buffer: a header
+ *    stands there, or -- that one being damaged in place -- the bytes two frames
+ *    later lie inside the buffer too and a header stands there (the reference's
+ *    recovery searches with check=1 and accepts a header two frames on when the
+ *    next one is bad: vdif/base.py:655-690);
+ *  - else (the last frame of the buffer): p < frame_nbytes, or a header stands
+ *    one frame EARLIER (check=-1).
+ * In terms of locate_frames from position 0 with maximum = nbytes: its answer
+ * for check=(1,), or for check=(2,), in the first case and for check=(-1,) in
+ * the second (tests/golden/locate_whole_cases.json records all three).
+ * Every byte inside the buffer is seen, whatever the alignment of p and
+ * nbytes; nothing behind nbytes is read.  frame_nbytes < 32: nothing is found.
  * Offsets are appended UNORDERED to d_offsets (capacity `cap`); *d_count
  * (device, caller-zeroed) receives the total number found.  bb_vdif_scan_at()
  * then produces the usual records for explicit, possibly unaligned offsets.
@@ -209,6 +230,15 @@ typedef struct bb_mark5b_scan_params {
                                * index and checks nothing (base/base.py:1003-1010) */
 } bb_mark5b_scan_params;
 
+/* Records (bb_mark5b_scan and bb_mark5b_scan_at): payload_offset = frame offset
+ * + 16.  A frame that does not lie wholly inside the buffer has no header (its
+ * words read as zero) and is neither OK nor INVALID.  time_index = (jday * 86400
+ * + seconds - ref_seconds) * frame_rate + frame_nr - ref_frame_nr, where a
+ * difference below -500 days has 1000 days added (jday is the day modulo 1000,
+ * mark5b/header.py:235-262; a stream runs forward from header0); the frame's
+ * number in the call when frame_rate = 0 or by_position; clamped to
+ * +-(2^31 - 1).  BCD nibbles above 9 make the reference raise
+ * (base/utils.py:18-40); what the scan gives for them is not defined. */
 int bb_mark5b_scan(const void *d_buf, size_t nbytes,
                    const bb_mark5b_scan_params *params,
                    bb_frame_rec *d_recs, size_t nframes, void *stream);
@@ -219,8 +249,14 @@ int bb_mark5b_scan(const void *d_buf, size_t nbytes,
  * Mark5BFileReader.find_header, mark5b/base.py:136-155, and locate_frames,
  * base/base.py:181-335).  bb_mark5b_locate tests EVERY byte offset: a frame
  * starts at p when the sync word 0xABADDEED sits there, the 10016-byte frame
- * fits in the buffer, the BCD time code passes its CRC-16, and -- when four
- * bytes still fit there -- another sync word sits one frame later (check=1).
+ * fits in the buffer, the BCD time code passes its CRC-16 (whatever its
+ * nibbles: the search does not decode them), and -- when MORE than four bytes
+ * lie behind the frame (p + 10016 + 4 < nbytes) -- another sync word sits one
+ * frame later (check=1; the reference looks at a check point c only when
+ * `c < stop - offset - pattern.size`, base/base.py:329-333, strictly: a file
+ * with exactly four bytes of anything behind its last frame keeps that frame).
+ * A sync word that lies inside the buffer is seen whole, whatever the
+ * alignment of p and of nbytes; nothing behind nbytes is read.
  * Offsets are appended unordered to d_offsets (at most `cap`; *d_count, which
  * the caller zeroes, receives the number found).  bb_mark5b_scan_at is
  * bb_mark5b_scan for frames at explicit, possibly odd, offsets
@@ -243,9 +279,12 @@ int bb_mark5b_locate(const void *d_buf, size_t nbytes, int64_t *d_offsets,
                      size_t cap, unsigned long long *d_count, void *stream);
 /* ... for ONE stream: word 1 of the header must also agree with `w1_pattern` under
  * `w1_mask` (the bits header0.invariant_pattern() marks in that word: the user
- * word, mark5b/header.py:70-73), at p and -- when it still fits -- one frame
- * later, as the stream reader's searches do, which hand header0 to locate_frames
- * (base/base.py:1083-1219).  w1_mask = 0: bb_mark5b_locate. */
+ * word, mark5b/header.py:70-73), at p and one frame later, as the stream
+ * reader's searches do, which hand header0 to locate_frames
+ * (base/base.py:1083-1219).  The pattern is then eight bytes long: sync word and
+ * word 1 one frame later are looked at when MORE than eight bytes lie behind the
+ * frame, and not at all otherwise (the reference's rule for a mask whose top byte
+ * carries bits, as the user word's does).  w1_mask = 0: bb_mark5b_locate. */
 int bb_mark5b_locate_stream(const void *d_buf, size_t nbytes, uint32_t w1_pattern, uint32_t w1_mask,
                             int64_t *d_offsets, size_t cap, unsigned long long *d_count, void *stream);
 int bb_mark5b_scan_at(const void *d_buf, size_t nbytes,
@@ -459,6 +498,16 @@ typedef struct bb_mark4_scan_params {
     int32_t  by_position;     /* nonzero: as for bb_mark5b_scan_params (verify=False) */
 } bb_mark4_scan_params;
 
+/* Records (bb_mark4_scan and bb_mark4_scan_at).  A frame that does not lie
+ * wholly inside the buffer has an all-zero header and is not OK.  Track 0's
+ * time q: a unit-year digit equal to (ref_year + 1) % 10 adds the length of
+ * ref_year (366 days in a leap year), any digit other than that and ref_year's
+ * own is not OK.  time_index = (q - ref_qms) / frame_qms rounded half away from
+ * zero and clamped to +-(2^31 - 1); not OK unless the division is exact.  A BCD
+ * nibble above 9 in the time code counts at face value (nibble times its power
+ * of ten) and makes the record not OK (the reference raises).  frame_qms = 0:
+ * time_index = the frame's number in the call.  by_position: OK = the frame is
+ * whole, nothing else is looked at. */
 int bb_mark4_scan(const void *d_buf, size_t nbytes,
                   const bb_mark4_scan_params *params,
                   bb_frame_rec *d_recs, size_t nframes, void *stream);
@@ -485,8 +534,10 @@ int bb_mark4_header_crc(const void *d_buf, size_t nbytes, int ntrack,
  * base/base.py:1127-1219, with Mark4FileReader.locate_frames,
  * mark4/base.py:110-166).  bb_mark4_locate tests EVERY byte offset: a frame
  * starts at p when stream word 63 is zero and words 64..95 are all ones, the
- * ntrack*2500-byte frame fits in the buffer, and -- when its pattern still
- * fits -- the frame one later shows the same pattern (check=1).  Output as
+ * ntrack*2500-byte frame fits in the buffer, and -- when MORE than the first 96
+ * stream words of the frame one later lie inside the buffer (strictly, as in
+ * locate_frames, base/base.py:329-333) -- that frame shows the same pattern
+ * (check=1).  Output as
  * for bb_mark5b_locate.  bb_mark4_scan_at is bb_mark4_scan for frames at
  * explicit offsets (need not be word aligned; params->first_offset ignored).
  */
