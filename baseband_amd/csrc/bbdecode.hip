@@ -2117,7 +2117,11 @@ int bb_encode_flat(const float *d_in, size_t nelem, int coder, int bps,
     // 4-bit codes (16-bit stores) gain from two runs per wave, 5.57 -> 6.05 TB/s at
     // 32 GiB in; every other width loses 1-8 % (profiles/r03zj_exp_encode_runs.log)
     const int eknob = g_tune_encode_runs.load();
-    const int eruns = eknob ? eknob : (bps == 4 ? 2 : 1);
+    // (the kernel with two runs exists for 4-bit codes, and for every width in the
+    // experiment build: elsewhere the knob must not shrink the grid or show in the name)
+    const bool direct = g_tune_encode_direct.load() != 0;
+    const int eruns = (direct && bps == 2) ? 1
+                    : (bps == 4 || BB_EXP) ? (eknob ? eknob : (bps == 4 ? 2 : 1)) : 1;
     uint64_t blocks = (nquad / 256 / eruns + 3) / 4 + 1;  // RUNS 256-quad runs per wave
     // one run per wave and as many workgroups as that takes: the encoder is a
     // streaming read without a software pipeline, the dispatcher overlaps it
@@ -2129,7 +2133,6 @@ int bb_encode_flat(const float *d_in, size_t nelem, int coder, int bps,
     const dim3 grid((unsigned)blocks), block(BB_BLOCK);
     hipStream_t st = (hipStream_t)stream;
     uint8_t *o = (uint8_t *)d_out;
-    const bool direct = g_tune_encode_direct.load() != 0;
     bb_perm_t perm = {0, 0, 0};
     const int elw = g_tune_encode_lw.load();
     if (elw > 0 && ((nquad >> 8) >> elw) >= 64) {
@@ -2147,8 +2150,9 @@ int bb_encode_flat(const float *d_in, size_t nelem, int coder, int bps,
         if (bps == 4) BB_E(BB_CODER_INT, 4); else BB_E(BB_CODER_INT, 8);
     }
 #undef BB_E
-    BB_NOTE("k_encode_flat<%s,%d,%s,%d> grid %u", coder == BB_CODER_VDIF ? "VDIF" : coder == BB_CODER_MARK5B ? "MARK5B" : "INT",
-            bps, direct && bps == 2 ? "direct" : "thresholds", eruns, grid.x);
+    BB_NOTE("k_encode_flat<%s,%d,%s,%d> grid %u stripes %u", coder == BB_CODER_VDIF ? "VDIF" : coder == BB_CODER_MARK5B ? "MARK5B" : "INT",
+            bps, direct && bps == 2 ? "direct" : "thresholds", eruns, grid.x,
+            perm.n ? 1u << perm.lw : 0u);
     BB_HIP(hipGetLastError());
     return BB_OK;
 }

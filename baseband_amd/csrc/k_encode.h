@@ -34,8 +34,11 @@ __host__ __device__ __forceinline__ float bb_np_floor_divide_hd(float a, float b
 // bb_init() finds them by bisection over the float32 bit patterns with the
 // exact reference arithmetic (bb_encode2_reference below, compiled for the
 // host), so the default path is three compares per sample.  DIRECT evaluates
-// the reference arithmetic on the device instead (BB_TUNE_ENCODE_DIRECT; the
-// GPU tests check both paths against each other over all 2^32 inputs).
+// the reference arithmetic on the device instead (BB_TUNE_ENCODE_DIRECT).
+// The GPU tests run every non-NaN float32 through both paths, and through
+// every other coder of this file, and compare the places where the code
+// changes with the NumPy oracle on the CPU (tests/test_encode_oracle_gpu.py);
+// the older test of both paths against each other over all 2^32 inputs stays.
 __device__ float g_enc2_thr[3];
 
 __host__ __device__ __forceinline__ float bb_np_floor_divide_hd(float a, float b);

@@ -719,12 +719,23 @@ def as_device_samples(data):
     return data.to(device='cuda', dtype=want)
 
 
+def _encode_input(values):
+    """Samples as the encode kernels read them: flat contiguous float32 that
+    starts on a 16-byte boundary (they load float4).  A contiguous view that
+    starts elsewhere in its storage (`samples[1:]`) is copied; an aligned
+    tensor is handed on as it is."""
+    values = values.to(torch.float32).contiguous().reshape(-1)
+    if values.data_ptr() % 16:
+        values = values.clone()
+    return values
+
+
 def encode_flat(values, coder, bps):
     """float32 (or complex64) device tensor -> packed uint8 device tensor."""
     require_gpu()
     if values.is_complex():
         values = torch.view_as_real(values)
-    values = values.to(torch.float32).contiguous().reshape(-1)
+    values = _encode_input(values)
     nbytes = values.numel() * bps // 8 if bps in (1, 2, 4, 8) else 0
     # the kernel packs quads of samples into whole bytes: a shorter tail (item
     # assignment of a few samples) is padded here and cut off the output
@@ -742,7 +753,7 @@ def encode_flat(values, coder, bps):
 def encode_mark4(values, ntrack, sign_bit, mag_bit):
     """(nsample, nchan) float32 device tensor -> stream words as uint8."""
     require_gpu()
-    values = values.to(torch.float32).contiguous().reshape(-1)
+    values = _encode_input(values)
     opw = ntrack // 2
     nwords = values.numel() // opw
     sb = (C.c_uint8 * 32)(*sign_bit)

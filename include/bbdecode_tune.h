@@ -32,7 +32,7 @@ extern "C" {
 #define BB_TUNE_LUT_TILES     24   /* upper bound of 256-byte tiles per wave and work item of the byte-table kernels, stated for 2-bit samples (1..16; half as many for 1-bit, twice as many for 4-bit samples).  Default 0 = by kernel: 4 (32 KiB of output per work item) for k_decode_flat_lut (1- and 4-bit), 6 (48 KiB) for the 2-bit kernel k_decode_flat_lds */
 #define BB_TUNE_XPOSE_TC      27   /* k_decode_i8_xpose: channels per tile, 64 / 32 / 16 / 8; default 0 = 32 for channels-first blocks, 16 for time-first blocks, 64 for MKBF heaps, and never wider than the decoded channels need */
 #define BB_TUNE_XPOSE_MIN_NC  28   /* blocks decoded whole go through k_decode_i8_xpose from this many channels on (default 8; selections: always from 2) */
-#define BB_TUNE_ENCODE_RUNS   30   /* k_encode_flat: runs of 256 float4 a wave takes per step, all loads in flight first: 1 or 2; default 0 = 2 for 4-bit codes, 1 otherwise (the product library builds 2 for 4-bit codes only) */
+#define BB_TUNE_ENCODE_RUNS   30   /* k_encode_flat: runs of 256 float4 a wave takes per step, all loads in flight first: 1 or 2; default 0 = 2 for 4-bit codes, 1 otherwise (the product library builds 2 for 4-bit codes only and ignores the knob for every other width) */
 #define BB_TUNE_M4_TILES      26   /* 64-word tiles per wave and work item of the Mark 4 decode kernels (1..8, default 8) */
 #define BB_TUNE_GATHER_GLDS   36   /* the LDS gather kernels stage payload bytes with direct-to-LDS loads (1) or load + ds_write (0); default -1 = by kernel: folded channel subsets (k_decode_gather_select) yes, whole thread interleaves (k_decode_gather) no */
 #define BB_TUNE_SELECT_PICK    39   /* folded channel subsets: 1 (default) = k_decode_pick (one work item per wave, direct-to-LDS 16-byte loads) for selections of up to an eighth of a thread sample where its conditions hold, 2 = wherever they hold, 0 = k_decode_gather_select always */
