@@ -181,20 +181,11 @@ int decode_frames(const bb_decode_params *p, const int64_t *d_src, size_t nframe
     // (profiles/r02ba_exp_int8_seg.log)
     const int seg_knob = g_tune_seg_tiles.load();
     const uint64_t seg_plain = seg_knob ? (uint64_t)seg_knob : (p->bps == 8 ? 16u : (uint64_t)BB_SEG_TILES);
-    a.nseg = (ntiles + seg_plain - 1) / seg_plain;
-    // split a frame-slot's tiles evenly over its work items and a work item's
-    // tiles evenly over the four waves (a 10000-byte Mark 5B payload is 40
-    // tiles: 2 items x 20 tiles x 5 per wave, not 32 + 8)
-    a.seg_tiles = (uint32_t)((ntiles + a.nseg - 1) / a.nseg);
-    a.tpw = (a.seg_tiles + BB_WAVES_PER_BLOCK - 1) / BB_WAVES_PER_BLOCK;
+    split_tiles(a, ntiles, seg_plain, BB_WAVES_PER_BLOCK);
     const uint64_t nwork = nfs * a.nseg;
     const uint64_t out_bytes = nfs * E * 4;
     a.perm = make_perm(nwork, out_bytes);   // (branches that cut the work differently set their own)
-    uint64_t blocks = nwork;
-    const int tb = g_tune_blocks.load();
-    if (tb > 0 && blocks > (uint64_t)tb) blocks = (uint64_t)tb;
-    if (blocks > 0x7fffffffull) blocks = 0x7fffffffull;
-    const dim3 grid((unsigned)blocks);
+    const dim3 grid = capped_grid(nwork, BB_GRID_MAX);
     const bool nt = g_tune_nt.load() != 0;
 
     // Kernel choice.  The default (5) is the persistent pipelined family with
@@ -272,12 +263,10 @@ int decode_frames(const bb_decode_params *p, const int64_t *d_src, size_t nframe
     }
 
     if (variant == 1 && p->bps == 2 && om == BB_OUT_FLAT) {
-        uint64_t b2 = nfs;
-        if (tb > 0 && b2 > (uint64_t)tb) b2 = (uint64_t)tb;
-        if (b2 > 0x7fffffffull) b2 = 0x7fffffffull;
-        if (nt) hipLaunchKernelGGL(k_decode_flat2_bytes<true>, dim3((unsigned)b2), dim3(BB_BLOCK), 0, st, a);
-        else    hipLaunchKernelGGL(k_decode_flat2_bytes<false>, dim3((unsigned)b2), dim3(BB_BLOCK), 0, st, a);
-        BB_NOTE("k_decode_flat2_bytes<%s> grid %u", nt ? "nt" : "plain", (unsigned)b2);
+        const dim3 g2 = capped_grid(nfs, BB_GRID_MAX);
+        if (nt) hipLaunchKernelGGL(k_decode_flat2_bytes<true>, g2, dim3(BB_BLOCK), 0, st, a);
+        else    hipLaunchKernelGGL(k_decode_flat2_bytes<false>, g2, dim3(BB_BLOCK), 0, st, a);
+        BB_NOTE("k_decode_flat2_bytes<%s> grid %u", nt ? "nt" : "plain", g2.x);
         BB_HIP(hipGetLastError());
         return BB_OK;
     }
@@ -322,7 +311,7 @@ int decode_frames(const bb_decode_params *p, const int64_t *d_src, size_t nframe
         {
             const uint32_t rl = (uint32_t)p->nslot * (uint32_t)p->chunk;
             ga.lrow = -1;
-            if ((rl & (rl - 1)) == 0) { ga.lrow = 0; while ((1u << ga.lrow) < rl) ++ga.lrow; }
+            if ((rl & (rl - 1)) == 0) ga.lrow = (int32_t)ceil_log2(rl);
         }
         ga.aligned = variant >= 5 ? 1 : 0;
         ga.glds = 0;
@@ -330,12 +319,8 @@ int decode_frames(const bb_decode_params *p, const int64_t *d_src, size_t nframe
         // persistent grid: a workgroup walks about five work items (8 KiB of
         // payload each); one workgroup per item costs 15 %, a few thousand
         // long-running ones 5-10 % (profiles/r01f_exp_gather*.log)
-        uint64_t gb = (uint64_t)nframes * ga.ngroup;
-        ga.perm = make_perm(gb, out_bytes);
-        const uint64_t gcap = tb > 0 ? (uint64_t)tb : BB_GRID_CAP;
-        if (gb > gcap) gb = gcap;
-        if (gb > 0x7fffffffull) gb = 0x7fffffffull;
-        const dim3 gg((unsigned)gb);
+        ga.perm = make_perm((uint64_t)nframes * ga.ngroup, out_bytes);
+        const dim3 gg = capped_grid((uint64_t)nframes * ga.ngroup, BB_GRID_CAP);
         switch (p->bps) {
             case 1: launch_gather<1, BB_LV_REG>(nt, gg, lds, st, ga); break;
             case 2: launch_gather<2, BB_LV_REG>(nt, gg, lds, st, ga); break;
@@ -357,15 +342,10 @@ int decode_frames(const bb_decode_params *p, const int64_t *d_src, size_t nframe
         const int nw = p->nslot >= 8 ? 8 : (p->nslot >= 4 ? 4 : 2);
         const bool aln = variant >= 5;
         const uint64_t seg_max = g_tune_tpw.load() < 8 ? (uint64_t)g_tune_tpw.load() : 8;
-        a.nseg = (ntiles + seg_max - 1) / seg_max;
-        a.seg_tiles = (uint32_t)((ntiles + a.nseg - 1) / a.nseg);
-        a.tpw = a.seg_tiles;
+        split_tiles(a, ntiles, seg_max, 1);
         const uint64_t sgroups = ((uint64_t)p->nslot + nw - 1) / nw;
-        uint64_t b2 = (uint64_t)nframes * a.nseg * sgroups;
-        a.perm = make_perm(b2, out_bytes);
-        const uint64_t cap = tb > 0 ? (uint64_t)tb : BB_GRID_CAP;
-        if (b2 > cap) b2 = cap;
-        const dim3 g2((unsigned)b2);
+        a.perm = make_perm((uint64_t)nframes * a.nseg * sgroups, out_bytes);
+        const dim3 g2 = capped_grid((uint64_t)nframes * a.nseg * sgroups, BB_GRID_CAP);
         switch (p->bps) {
             case 1: launch_rows_pipe<1, BB_LV_REG>(nt, aln, nw, g2, st, a); break;
             case 2: launch_rows_pipe<2, BB_LV_REG>(nt, aln, nw, g2, st, a); break;
@@ -385,10 +365,7 @@ int decode_frames(const bb_decode_params *p, const int64_t *d_src, size_t nframe
         // contiguous output: cut the work in output space (k_decode_flat_span),
         // 2 waves x 16 tiles per item whatever the frame size
         const uint64_t tiles_all = (nfs * a.ndw + 63) / 64;
-        uint64_t b2 = (tiles_all + 31) / 32;
-        const uint64_t cap = tb > 0 ? (uint64_t)tb : BB_GRID_CAP;
-        if (b2 > cap) b2 = cap;
-        const dim3 g2((unsigned)b2);
+        const dim3 g2 = capped_grid((tiles_all + 31) / 32, BB_GRID_CAP);
         switch (p->bps) {
             case 1: launch_flat_span<1, BB_LV_REG>(nt, g2, st, a); break;
             case 2: launch_flat_span<2, BB_LV_REG>(nt, g2, st, a); break;
@@ -433,14 +410,9 @@ int decode_frames(const bb_decode_params *p, const int64_t *d_src, size_t nframe
         const int tpw_max = long8 ? (tpw8 > 32 ? 32 : tpw8) : lut ? lut_tiles
                             : wide ? g_tune_tpw.load() : 8;
         const uint64_t seg_max = (uint64_t)nw * tpw_max;
-        a.nseg = (ntiles + seg_max - 1) / seg_max;
-        a.seg_tiles = (uint32_t)((ntiles + a.nseg - 1) / a.nseg);
-        a.tpw = (a.seg_tiles + nw - 1) / nw;
-        uint64_t b2 = nfs * a.nseg;
-        a.perm = make_perm(b2, out_bytes);
-        const uint64_t cap = tb > 0 ? (uint64_t)tb : lut ? (1ull << 23) : (uint64_t)(wide ? BB_GRID_CAP : 4096);
-        if (b2 > cap) b2 = cap;
-        const dim3 g2((unsigned)b2);
+        split_tiles(a, ntiles, seg_max, nw);
+        a.perm = make_perm(nfs * a.nseg, out_bytes);
+        const dim3 g2 = capped_grid(nfs * a.nseg, lut ? BB_GRID_SHORT_ITEMS : (uint64_t)(wide ? BB_GRID_CAP : 4096));
         if (!wide) {
             switch (p->bps) {
                 case 1: launch_flat_pipe<1, BB_LV_REG, 4, 8>(om, nt, g2, st, a); break;

@@ -304,6 +304,62 @@ bb_perm_t make_perm(uint64_t nwork, uint64_t out_bytes, bb_order_family family =
     return p;
 }
 
+// ---- launch arithmetic every entry shares ----------------------------------------
+inline uint32_t ceil_log2(uint64_t x) { uint32_t l = 0; while ((1ull << l) < x) ++l; return l; }
+
+// The tiles of a frame-slot (or Mark 4 unit) are split evenly over its work items of at
+// most `tiles_per_item`, and a work item's tiles evenly over its `waves` (a 10000-byte
+// Mark 5B payload is 40 tiles: for the plain kernel 2 items x 20 tiles x 5 per wave, not
+// 32 + 8).
+template <class Args>
+inline void split_tiles(Args &a, uint64_t ntiles, uint64_t tiles_per_item, uint64_t waves)
+{
+    a.nseg = (ntiles + tiles_per_item - 1) / tiles_per_item;
+    a.seg_tiles = (uint32_t)((ntiles + a.nseg - 1) / a.nseg);
+    a.tpw = (uint32_t)((a.seg_tiles + waves - 1) / waves);
+}
+
+// Grid of a launch whose workgroups walk `nwork` items: one workgroup per item up to
+// BB_TUNE_BLOCKS when that knob is set, else up to `default_cap`; never more than a grid
+// holds, never empty.
+inline dim3 capped_grid(uint64_t nwork, uint64_t default_cap)
+{
+    const int tb = g_tune_blocks.load();
+    const uint64_t cap = tb > 0 ? (uint64_t)tb : default_cap;
+    uint64_t blocks = nwork < cap ? nwork : cap;
+    if (blocks > 0x7fffffffull) blocks = 0x7fffffffull;
+    return dim3(blocks ? (unsigned)blocks : 1u);
+}
+#define BB_GRID_MAX 0x7fffffffull                    // capped_grid: one workgroup per item (the plain kernel, transposes, encoders)
+#define BB_GRID_SHORT_ITEMS (1ull << 23)             // ... short work items, one per workgroup (byte-table, 16-bit flat, Mark 4, copies)
+
+// Grid of the launches with one thread (or wave) per record: these do not loop.
+inline int record_grid(uint64_t n, uint64_t per_block, dim3 *grid)
+{
+    const uint64_t blocks = (n + per_block - 1) / per_block;
+    if (blocks > 0x7fffffffull) return BB_ERANGE;
+    *grid = dim3((unsigned)blocks);
+    return BB_OK;
+}
+
+// Grid of the byte-granular searches: BB_LOCATE_U x 16 bytes per lane and iteration.
+// (65536 workgroups: 5.1-5.8 TB/s on the 8 GiB image, 16384: 5.0-5.2, 131072: 4.3-4.4;
+// profiles/r04l_locate.log -- the workgroups' confirm phases overlap other workgroups' sweeps)
+inline dim3 locate_grid(size_t nbytes)
+{
+    return capped_grid((nbytes / 16 + BB_BLOCK * BB_LOCATE_U - 1) / (BB_BLOCK * BB_LOCATE_U), BB_LOCATE_GRID);
+}
+
+// A source without an index: unit f of `n` (>= 1) starts at src0 + f * stride, both
+// multiples of `align` (a power of two) and not negative, and the last unit's `span`
+// bytes end inside the buffer.
+inline int fixed_stride_check(int64_t src0, int64_t stride, uint64_t align, uint64_t n, uint64_t span, size_t buf_nbytes)
+{
+    if (src0 < 0 || stride < 0 || (((uint64_t)src0 | (uint64_t)stride) & (align - 1))) return BB_EINVAL;
+    if ((uint64_t)src0 + (n - 1) * (uint64_t)stride + span > buf_nbytes) return BB_ERANGE;
+    return BB_OK;
+}
+
 // (bits per sample, coder) -> kernel template arguments <BPS, LV>
 template <class F>
 inline void with_levels(int bps, int coder, F &&f)
@@ -537,6 +593,18 @@ int decode_params_check(const bb_decode_params *p)
     return BB_OK;
 }
 
+// What bb_decode_frames asks of its buffers, for a parameter block that has passed the
+// check above: pointers, alignment, an output of `nfs` frame-slots (in elements of the
+// output type) and, without an index, the source range.
+int decode_buffers_check(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, uint64_t nfs,
+                         const bb_decode_params *p, const void *d_out, size_t out_elems)
+{
+    if (!d_buf || !d_out) return BB_EINVAL;
+    if (((uintptr_t)d_buf & 3) || ((uintptr_t)d_out & 15)) return BB_EINVAL;
+    if (out_elems < nfs * (p->payload_nbytes * 8 / (uint64_t)p->bps)) return BB_ERANGE;
+    return d_src ? BB_OK : fixed_stride_check(p->src0, p->src_stride, 4, nfs, p->payload_nbytes, buf_nbytes);
+}
+
 inline uint16_t half_pattern(int out_type, float x)
 {
     return out_type == BB_OUT_F16 ? bb_f32_to_f16(x) : bb_f32_to_bf16(x);
@@ -562,16 +630,10 @@ int decode_half(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size
     int rc = decode_params_check(p);
     if (rc) return rc;
     if (nframes == 0) return BB_OK;
-    if (!d_buf || !d_out) return BB_EINVAL;
-    if (((uintptr_t)d_buf & 3) || ((uintptr_t)d_out & 15)) return BB_EINVAL;
     const uint64_t E = p->payload_nbytes * 8 / (uint64_t)p->bps;
     const uint64_t nfs = (uint64_t)nframes * (uint64_t)p->nslot;
-    if (out_elems < nfs * E) return BB_ERANGE;
-    if (!d_src) {
-        if ((p->src0 & 3) || (p->src_stride & 3) || p->src0 < 0 || p->src_stride < 0) return BB_EINVAL;
-        if ((uint64_t)p->src0 + (nfs - 1) * (uint64_t)p->src_stride + p->payload_nbytes > buf_nbytes)
-            return BB_ERANGE;
-    }
+    rc = decode_buffers_check(d_buf, buf_nbytes, d_src, nfs, p, d_out, out_elems);
+    if (rc) return rc;
     rc = ensure_init();
     if (rc) return rc;
     bb_half_args a;
@@ -585,8 +647,7 @@ int decode_half(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size
     a.nseg = 1; a.seg_tiles = 0; a.tpw = 0; a.seg_bytes = 0;
     a.nslot = (uint32_t)p->nslot;
     a.chunk = (uint32_t)p->chunk;
-    a.lchunk = 0;
-    while ((1u << a.lchunk) < a.chunk) ++a.lchunk;
+    a.lchunk = ceil_log2(a.chunk);
     const uint16_t fre = half_pattern(p->out_type, p->fill_re);
     const uint16_t fim = p->complex_data ? half_pattern(p->out_type, p->fill_im) : fre;
     a.fill = (uint32_t)fre | ((uint32_t)fim << 16);
@@ -595,7 +656,6 @@ int decode_half(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size
     a.src_lim = src_limit(buf_nbytes, p->payload_nbytes);
     hipStream_t st = (hipStream_t)stream;
     const uint64_t out_bytes = nfs * E * 2;
-    const int tb = g_tune_blocks.load();
     const char *tname = p->out_type == BB_OUT_F16 ? "f16" : "bf16";
 
     if (p->nslot == 1) {
@@ -607,15 +667,9 @@ int decode_half(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size
         int tiles = g_tune_lut_tpw.load();
         if (tiles == 0) tiles = p->bps == 1 ? 4 : 8;
         tiles = tiles < 1 ? 1 : tiles > 8 ? 8 : tiles;
-        const uint64_t seg_max = 2ull * (uint64_t)tiles;
-        a.nseg = (ntiles + seg_max - 1) / seg_max;
-        a.seg_tiles = (uint32_t)((ntiles + a.nseg - 1) / a.nseg);
-        a.tpw = (a.seg_tiles + 1) / 2;
-        uint64_t b2 = nfs * a.nseg;
-        a.perm = make_perm(b2, out_bytes, BB_ORDER_FLAT);
-        const uint64_t cap = tb > 0 ? (uint64_t)tb : (1ull << 23);
-        if (b2 > cap) b2 = cap;
-        const dim3 g2((unsigned)b2);
+        split_tiles(a, ntiles, 2ull * (uint64_t)tiles, 2);
+        a.perm = make_perm(nfs * a.nseg, out_bytes, BB_ORDER_FLAT);
+        const dim3 g2 = capped_grid(nfs * a.nseg, BB_GRID_SHORT_ITEMS);
         launch_half(p->bps, [&](auto B) {
             hipLaunchKernelGGL((k_decode_half_flat<decltype(B)::value, 2, 8>), g2, dim3(2 * BB_WAVE), 0, st, a);
         });
@@ -630,11 +684,8 @@ int decode_half(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size
     while (sb < 4096 && (uint64_t)sb * 2 * (uint64_t)p->nslot <= 16384) sb *= 2;
     a.seg_bytes = sb;
     a.nseg = (p->payload_nbytes + sb - 1) / sb;
-    uint64_t gb = (uint64_t)nframes * a.nseg;
-    a.perm = make_perm(gb, out_bytes, BB_ORDER_GATHER);
-    const uint64_t gcap = tb > 0 ? (uint64_t)tb : BB_GRID_CAP;
-    if (gb > gcap) gb = gcap;
-    const dim3 gg((unsigned)gb);
+    a.perm = make_perm((uint64_t)nframes * a.nseg, out_bytes, BB_ORDER_GATHER);
+    const dim3 gg = capped_grid((uint64_t)nframes * a.nseg, BB_GRID_CAP);
     const size_t lds = (size_t)p->nslot * (8 + (size_t)sb);
     launch_half(p->bps, [&](auto B) {
         hipLaunchKernelGGL((k_decode_half_rows<decltype(B)::value>), gg, dim3(BB_BLOCK), lds, st, a);
@@ -810,10 +861,9 @@ static int vdif_scan_impl(const void *d_buf, size_t nbytes, const bb_vdif_scan_p
     if (p->header_nbytes != 32 && p->header_nbytes != 16) return BB_EINVAL;
     if (p->frame_nbytes < p->header_nbytes || (p->frame_nbytes & 7)) return BB_EINVAL;
     if ((p->first_offset & 3) || ((uintptr_t)d_buf & 3)) return BB_EINVAL;
-    const uint64_t threads = (uint64_t)nframes * 8;
-    const uint64_t blocks = (threads + BB_BLOCK - 1) / BB_BLOCK;
-    if (blocks > 0x7fffffffull) return BB_ERANGE;
-    hipLaunchKernelGGL(k_vdif_scan, dim3((unsigned)blocks), dim3(BB_BLOCK), 0, (hipStream_t)stream,
+    dim3 grid;                                          // (8 threads per frame)
+    if (int rc = record_grid((uint64_t)nframes * 8, BB_BLOCK, &grid)) return rc;
+    hipLaunchKernelGGL(k_vdif_scan, grid, dim3(BB_BLOCK), 0, (hipStream_t)stream,
                        (const uint8_t *)d_buf, (uint64_t)nbytes, *p, d_recs, (uint64_t)nframes, d_fill, (uint64_t)fill_n);
     BB_HIP(hipGetLastError());
     return BB_OK;
@@ -835,9 +885,9 @@ static int index_verify(const bb_frame_rec *d_recs, size_t nrecs, const int16_t 
     if (!prefilled && nframes_out)
         BB_HIP(hipMemsetAsync(d_src, 0xff, nframes_out * (size_t)nslot * sizeof(int64_t), st));
     if (nrecs == 0) return BB_OK;
-    const uint64_t blocks = ((uint64_t)nrecs + BB_BLOCK - 1) / BB_BLOCK;
-    if (blocks > 0x7fffffffull) return BB_ERANGE;
-    hipLaunchKernelGGL(k_index_verify, dim3((unsigned)blocks), dim3(BB_BLOCK), 0, st, d_recs, (uint64_t)nrecs,
+    dim3 grid;
+    if (int rc = record_grid(nrecs, BB_BLOCK, &grid)) return rc;
+    hipLaunchKernelGGL(k_index_verify, grid, dim3(BB_BLOCK), 0, st, d_recs, (uint64_t)nrecs,
                        d_thread_slot, nslot, d_src, (uint64_t)nframes_out, recs_per_index, (uint64_t)nstrict, d_nbad);
     BB_HIP(hipGetLastError());
     return BB_OK;
@@ -851,13 +901,7 @@ int bb_vdif_locate(const void *d_buf, size_t nbytes, const bb_vdif_scan_params *
     if (p->frame_nbytes < p->header_nbytes) return BB_EINVAL;
     if ((uintptr_t)d_buf & 15) return BB_EINVAL;           // 16-byte loads (bb_locate_sweep)
     if (nbytes < p->frame_nbytes || p->frame_nbytes < 32) return BB_OK;
-    uint64_t blocks = (nbytes / 16 + BB_BLOCK * BB_LOCATE_U - 1) / (BB_BLOCK * BB_LOCATE_U);   // BB_LOCATE_U x 16 bytes per lane and iteration
-    // (65536 workgroups: 5.1-5.8 TB/s on the 8 GiB image, 16384: 5.0-5.2, 131072: 4.3-4.4;
-    // profiles/r04l_locate.log -- the workgroups' confirm phases overlap other workgroups' sweeps)
-    const uint64_t lcap = g_tune_blocks.load() > 0 ? (uint64_t)g_tune_blocks.load() : BB_LOCATE_GRID;
-    if (blocks > lcap) blocks = lcap;
-    if (blocks == 0) blocks = 1;
-    hipLaunchKernelGGL(k_vdif_locate, dim3((unsigned)blocks), dim3(BB_BLOCK), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(k_vdif_locate, locate_grid(nbytes), dim3(BB_BLOCK), 0, (hipStream_t)stream,
                        (const uint8_t *)d_buf, (uint64_t)nbytes, *p, d_offsets, (uint64_t)cap, d_count);
     BB_HIP(hipGetLastError());
     return BB_OK;
@@ -870,9 +914,9 @@ int bb_vdif_scan_at(const void *d_buf, size_t nbytes, const bb_vdif_scan_params 
     if (p->header_nbytes != 32 && p->header_nbytes != 16) return BB_EINVAL;
     if ((uintptr_t)d_buf & 3) return BB_EINVAL;
     if (nframes == 0) return BB_OK;
-    const uint64_t blocks = ((uint64_t)nframes + BB_BLOCK - 1) / BB_BLOCK;
-    if (blocks > 0x7fffffffull) return BB_ERANGE;
-    hipLaunchKernelGGL(k_vdif_scan_at, dim3((unsigned)blocks), dim3(BB_BLOCK), 0, (hipStream_t)stream,
+    dim3 grid;
+    if (int rc = record_grid(nframes, BB_BLOCK, &grid)) return rc;
+    hipLaunchKernelGGL(k_vdif_scan_at, grid, dim3(BB_BLOCK), 0, (hipStream_t)stream,
                        (const uint8_t *)d_buf, (uint64_t)nbytes, *p, d_offsets, d_recs, (uint64_t)nframes);
     BB_HIP(hipGetLastError());
     return BB_OK;
@@ -885,9 +929,9 @@ static int mark5b_scan_impl(const void *d_buf, size_t nbytes, const bb_mark5b_sc
     if (nframes == 0) return BB_OK;
     if (!d_buf || !p || !d_recs) return BB_EINVAL;
     if ((!d_offsets && (p->first_offset & 3)) || ((uintptr_t)d_buf & 3)) return BB_EINVAL;
-    const uint64_t blocks = ((uint64_t)nframes + BB_WAVES_PER_BLOCK - 1) / BB_WAVES_PER_BLOCK;
-    if (blocks > 0x7fffffffull) return BB_ERANGE;
-    hipLaunchKernelGGL(k_mark5b_scan, dim3((unsigned)blocks), dim3(BB_BLOCK), 0, (hipStream_t)stream,
+    dim3 grid;                                          // (a wave per frame)
+    if (int rc = record_grid(nframes, BB_WAVES_PER_BLOCK, &grid)) return rc;
+    hipLaunchKernelGGL(k_mark5b_scan, grid, dim3(BB_BLOCK), 0, (hipStream_t)stream,
                        (const uint8_t *)d_buf, (uint64_t)nbytes, *p, d_offsets, d_recs,
                        (uint64_t)nframes);
     BB_HIP(hipGetLastError());
@@ -913,10 +957,7 @@ int bb_mark5b_locate_stream(const void *d_buf, size_t nbytes, uint32_t w1_patter
     if (!d_buf || !d_offsets || !d_count) return BB_EINVAL;
     if ((uintptr_t)d_buf & 15) return BB_EINVAL;           // 16-byte loads (bb_locate_sweep)
     if (nbytes < BB_M5B_FRAME) return BB_OK;
-    uint64_t blocks = (nbytes / 16 + BB_BLOCK * BB_LOCATE_U - 1) / (BB_BLOCK * BB_LOCATE_U);   // BB_LOCATE_U x 16 bytes per lane and iteration
-    if (blocks > (g_tune_blocks.load() > 0 ? (uint64_t)g_tune_blocks.load() : BB_LOCATE_GRID)) blocks = g_tune_blocks.load() > 0 ? (uint64_t)g_tune_blocks.load() : BB_LOCATE_GRID;
-    if (blocks == 0) blocks = 1;
-    hipLaunchKernelGGL(k_mark5b_locate, dim3((unsigned)blocks), dim3(BB_BLOCK), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(k_mark5b_locate, locate_grid(nbytes), dim3(BB_BLOCK), 0, (hipStream_t)stream,
                        (const uint8_t *)d_buf, (uint64_t)nbytes, w1_pattern, w1_mask, d_offsets, (uint64_t)cap, d_count);
     BB_HIP(hipGetLastError());
     return BB_OK;
@@ -933,9 +974,9 @@ int bb_verify_records(const bb_frame_rec *d_recs, size_t nrecs, int32_t first_in
 {
     if (!d_nbad || (nrecs && !d_recs) || recs_per_index == 0) return BB_EINVAL;
     if (nrecs == 0) return BB_OK;
-    const uint64_t blocks = ((uint64_t)nrecs + BB_BLOCK - 1) / BB_BLOCK;
-    if (blocks > 0x7fffffffull) return BB_ERANGE;
-    hipLaunchKernelGGL(k_verify_records, dim3((unsigned)blocks), dim3(BB_BLOCK), 0, (hipStream_t)stream,
+    dim3 grid;
+    if (int rc = record_grid(nrecs, BB_BLOCK, &grid)) return rc;
+    hipLaunchKernelGGL(k_verify_records, grid, dim3(BB_BLOCK), 0, (hipStream_t)stream,
                        d_recs, (uint64_t)nrecs, first_index, recs_per_index, (uint64_t)nstrict, d_nbad);
     BB_HIP(hipGetLastError());
     return BB_OK;
@@ -950,10 +991,205 @@ int bb_build_index(const bb_frame_rec *d_recs, size_t nrecs,
     if (nframes_out)
         BB_HIP(hipMemsetAsync(d_src, 0xff, nframes_out * (size_t)nslot * sizeof(int64_t), st));
     if (nrecs == 0) return BB_OK;
-    const uint64_t blocks = ((uint64_t)nrecs + BB_BLOCK - 1) / BB_BLOCK;
-    if (blocks > 0x7fffffffull) return BB_ERANGE;
-    hipLaunchKernelGGL(k_build_index, dim3((unsigned)blocks), dim3(BB_BLOCK), 0, st,
+    dim3 grid;
+    if (int rc = record_grid(nrecs, BB_BLOCK, &grid)) return rc;
+    hipLaunchKernelGGL(k_build_index, grid, dim3(BB_BLOCK), 0, st,
                        d_recs, (uint64_t)nrecs, d_thread_slot, nslot, d_src, (uint64_t)nframes_out);
+    BB_HIP(hipGetLastError());
+    return BB_OK;
+}
+
+// Fields a gather launch of bb_decode_frames and of bb_decode_frames_select share; the
+// caller adds lrow, glds, perm and its selection.
+static bb_gather_args gather_args(const uint8_t *buf, const int64_t *d_src, float *d_out, const float *tab, size_t nframes,
+                                  const bb_decode_params *p, uint32_t lchunk, uint64_t src_lim, uint32_t gt, uint64_t ntiles)
+{
+    bb_gather_args ga;
+    ga.within = nullptr; ga.nsel = 0; ga.mag_row = ga.mag_sel = 0;
+    ga.buf = buf; ga.src = d_src; ga.out = d_out; ga.tab = tab;
+    ga.nframes = nframes; ga.ndw = p->payload_nbytes / 4;
+    ga.nslot = (uint32_t)p->nslot; ga.chunk = (uint32_t)p->chunk; ga.lchunk = lchunk;
+    ga.src_lim = src_lim;
+    ga.gtiles = gt;
+    ga.ngroup = (uint32_t)((ntiles + gt - 1) / gt);
+    ga.fill_re = p->fill_re; ga.fill_im = p->fill_im; ga.complex_data = p->complex_data;
+    ga.lrow = -1;
+    ga.aligned = 1;
+    return ga;
+}
+
+// ---- the launch branches of bb_decode_frames -----------------------------------------
+// Each takes the prepared argument block (nseg / seg_tiles / tpw / perm are the branch's to
+// set), the bytes the launch writes and the stream; which one runs: bb_decode_frames.
+static inline uint64_t flat_ntiles(const bb_flat_args &a) { return (a.ndw + 63) / 64; }
+
+// 1. thread interleave through the LDS gather (k_gather.h)
+static int decode_gather(const bb_decode_params *p, const bb_flat_args &a, uint64_t out_bytes, bool nt, hipStream_t st)
+{
+    const uint64_t ntiles = flat_ntiles(a), nframes = a.nfs / a.nslot;
+    // bytes staged per work item: 16 KiB, 4 KiB for 1-bit data whose items
+    // expand 32-fold (profiles/r01i_exp_interleave_gb.log); knob value 8192 = this default
+    size_t gbytes = (size_t)g_tune_gather_bytes.load();
+    if (gbytes == 8192) gbytes = p->bps == 1 ? 4096 : 16384;
+    uint32_t gt = (uint32_t)(gbytes / ((size_t)p->nslot * 256));
+    if (gt < 1) gt = 1;
+    if (gt > 32) gt = 32;
+    if ((uint64_t)gt > ntiles) gt = (uint32_t)ntiles;
+    bb_gather_args ga = gather_args(a.buf, a.src, a.out, a.tab, nframes, p, a.lchunk, a.src_lim, gt, ntiles);
+    const uint32_t rl = (uint32_t)p->nslot * (uint32_t)p->chunk;
+    if ((rl & (rl - 1)) == 0) ga.lrow = (int32_t)ceil_log2(rl);
+    ga.glds = g_tune_gather_glds.load() == 1;
+    const size_t lds = ((size_t)p->nslot * (gt * 64 + 65) + 2 * p->nslot + 1) * 4 + 1024;
+    // persistent grid: a workgroup walks about five work items (8 KiB of
+    // payload each); one workgroup per item costs 15 %, a few thousand
+    // long-running ones 5-10 % (profiles/r01f_exp_gather*.log)
+    const uint64_t nwork = nframes * ga.ngroup;
+    ga.perm = make_perm(nwork, out_bytes, BB_ORDER_GATHER);
+    const dim3 gg = capped_grid(nwork, BB_GRID_CAP);
+    launch_gather(p->bps, p->coder, nt, gg, lds, st, ga);
+    BB_NOTE("k_decode_gather<%d,%s,%s,%s> grid %u gtiles %u lds %zu", p->bps, lv_name(p->bps, p->coder),
+            nt ? "nt" : "plain", ga.lchunk >= 2 ? "wide" : "narrow", gg.x, ga.gtiles, lds);
+    BB_HIP(hipGetLastError());
+    return BB_OK;
+}
+
+// 2. thread interleave with wide chunks (k_decode_rows_pipe)
+static int decode_rows_pipe(const bb_decode_params *p, bb_flat_args &a, uint64_t out_bytes, bool nt, hipStream_t st)
+{
+    const int nw = p->nslot >= 8 ? 8 : (p->nslot >= 4 ? 4 : 2);
+    split_tiles(a, flat_ntiles(a), (uint64_t)g_tune_rows_tiles.load(), 1);
+    const uint64_t sgroups = ((uint64_t)p->nslot + nw - 1) / nw;
+    const uint64_t nwork = a.nfs / a.nslot * a.nseg * sgroups;
+    a.perm = make_perm(nwork, out_bytes, BB_ORDER_ROWS);
+    const dim3 g2 = capped_grid(nwork, BB_GRID_CAP);
+    launch_rows_pipe(p->bps, p->coder, nt, nw, g2, st, a);
+    BB_NOTE("k_decode_rows_pipe<%d,%s,%s,%d,8,aligned> grid %u", p->bps, lv_name(p->bps, p->coder),
+            nt ? "nt" : "plain", nw, g2.x);
+    BB_HIP(hipGetLastError());
+    return BB_OK;
+}
+
+// 3. contiguous 1-, 2- and 4-bit output: the byte table kernels (k_lut.h, k_lds.h)
+static int decode_flat_lut(const bb_decode_params *p, bb_flat_args &a, uint64_t out_bytes, bool nt, hipStream_t st)
+{
+    const uint64_t ntiles = flat_ntiles(a);
+#if BB_EXP
+    const int64_t *d_src = a.src;
+    float *d_out = a.out;
+    const uint64_t nfs = a.nfs;
+    const int tb = g_tune_blocks.load();
+    if (p->bps == 2 && g_tune_burst.load() != 0 && p->payload_nbytes >= 256) {
+        // 3a. the loader-wave kernel (k_burst.h): items of up to one staging buffer
+        bb_burst_args b;
+        b.buf = a.buf; b.src = d_src; b.out = d_out; b.tab = a.tab;
+        b.nfs = nfs; b.pbytes = p->payload_nbytes;
+        b.buf_bytes = (uint32_t)g_tune_burst_bytes.load();
+        const uint64_t fst = (b.pbytes + 30) & ~15ull;
+        if (fst <= b.buf_bytes) {
+            b.nseg = 1; b.seg_bytes = 0; b.fstride = (uint32_t)fst;
+            uint64_t k = b.buf_bytes / fst;
+            if (k > BB_BURST_MAXK) k = BB_BURST_MAXK;
+            b.kpi = (uint32_t)k;
+        } else {
+            b.seg_bytes = (b.buf_bytes - 32) & ~255u;
+            b.nseg = (b.pbytes + b.seg_bytes - 1) / b.seg_bytes;
+            b.fstride = b.buf_bytes; b.kpi = 1;
+        }
+        b.magic = (uint32_t)((1ull << 32) / b.pbytes) + 1;
+        const uint64_t nwork = nfs * b.nseg;
+        b.nitems = (nwork + b.kpi - 1) / b.kpi;
+        b.period = (uint32_t)g_tune_burst_period.load();
+        b.src0 = a.src0; b.src_stride = a.src_stride;
+        b.fill_re = a.fill_re; b.fill_im = a.fill_im; b.complex_data = a.complex_data;
+        b.src_lim = a.src_lim;
+        b.perm = make_perm(b.nitems, out_bytes);
+        const int nst = g_tune_burst_waves.load();
+        const size_t ldsb = BB_BURST_HEAD + 2 * (size_t)b.buf_bytes;
+        uint64_t per_cu = (160 * 1024) / ldsb;
+        const uint64_t by_waves = 32 / (uint64_t)(nst + 1);
+        if (per_cu > by_waves) per_cu = by_waves;
+        if (per_cu < 1) per_cu = 1;
+        uint64_t gb = tb > 0 ? (uint64_t)tb : 256 * per_cu;
+        if (gb > b.nitems) gb = b.nitems;
+        const dim3 gg((unsigned)gb);
+        int brc;
+        if (nst == 3) brc = launch_flat_burst<3>(nt, gg, ldsb, st, b);
+        else if (nst == 7) brc = launch_flat_burst<7>(nt, gg, ldsb, st, b);
+        else brc = launch_flat_burst<15>(nt, gg, ldsb, st, b);
+        if (brc) return brc;
+        BB_NOTE("k_decode_flat_burst<2,%s,%d> grid %u pieces/item %u buffer %u period %u", nt ? "nt" : "plain", nst,
+                gg.x, b.kpi, b.buf_bytes, b.period);
+        BB_HIP(hipGetLastError());
+        return BB_OK;
+    }
+#endif
+    bool lds = p->bps == 2 || p->bps == 4;
+#if BB_EXP
+    if (g_tune_variant.load() == 15 || (g_tune_variant.load() >= 19 && g_tune_variant.load() <= 25)) lds = true;        // A/B: force either kernel for every sample width
+    if (g_tune_variant.load() == 16) lds = false;
+#endif
+    // (2-bit through k_decode_flat_lds: 6 tiles per wave -- 0.851-0.859 of the peak with
+    // and without an index on three boxes, 4 tiles: 0.850-0.858 with, 0.837-0.848
+    // without; profiles/r04d_exp_glds3_box*.log.  Knob 0 = these defaults.)
+    const int lt_knob = g_tune_lut_tpw.load();
+    // (4-bit through k_decode_flat_lds: 4 tiles per wave; r04r_exp_glds5_box*.log)
+    int lut_tiles = lt_knob == 0 ? ((lds && p->bps == 2) ? 6 : (lds && p->bps == 4) ? 4 : 4 * p->bps / 2) : lt_knob * p->bps / 2;
+    lut_tiles = lut_tiles < 1 ? 1 : lut_tiles > (lds ? 8 : 16) ? (lds ? 8 : 16) : lut_tiles;
+    uint64_t nwv = 2;                                   // waves per workgroup
+#if BB_EXP
+    if (lds && p->bps == 2 && g_tune_variant.load() == 21) nwv = 4;     // A/B: 4 / 1 waves per workgroup
+    if (lds && p->bps == 2 && g_tune_variant.load() == 22) nwv = 1;
+#endif
+    split_tiles(a, ntiles, nwv * (uint64_t)lut_tiles, nwv);
+    a.perm = make_perm(a.nfs * a.nseg, out_bytes, BB_ORDER_FLAT);
+    const dim3 g2 = capped_grid(a.nfs * a.nseg, BB_GRID_SHORT_ITEMS);
+    if (lds) {
+#if BB_EXP
+        if (p->bps == 1) launch_flat_lds<1>(nt, g2, st, a);
+        else
+#endif
+        if (p->bps == 4) launch_flat_lds<4>(nt, g2, st, a);
+        else launch_flat_lds<2>(nt, g2, st, a);
+        const char *gl = "";
+#if BB_EXP
+        if (p->bps != 1 && g_tune_variant.load() == 19) gl = ",regs";
+        if (p->bps == 1 && g_tune_variant.load() == 20) gl = ",glds";
+#endif
+        BB_NOTE("k_decode_flat_lds<%d,%s,2,8%s> grid %u tiles/wave %u", p->bps, nt ? "nt" : "plain", gl, g2.x, a.tpw);
+    } else {
+        launch_flat_lut(p->bps, nt, g2, st, a);
+        BB_NOTE("k_decode_flat_lut<%d,%s,2,16> grid %u tiles/wave %u", p->bps, nt ? "nt" : "plain", g2.x, a.tpw);
+    }
+    BB_HIP(hipGetLastError());
+    return BB_OK;
+}
+
+// 3b. contiguous 8-bit output through k_decode_flat_lds<8>: 2 waves x `t8` tiles per item
+static int decode_flat_lds8(const bb_decode_params *p, bb_flat_args &a, int t8, bool gl8, uint64_t out_bytes, bool nt,
+                            hipStream_t st)
+{
+    split_tiles(a, flat_ntiles(a), 2ull * (uint64_t)t8, 2);
+    a.perm = make_perm(a.nfs * a.nseg, out_bytes, BB_ORDER_FLAT);
+    const dim3 g2 = capped_grid(a.nfs * a.nseg, BB_GRID_SHORT_ITEMS);
+    launch_flat_lds8(p->coder, nt, gl8, g2, st, a);
+    BB_NOTE("k_decode_flat_lds<8,%s,%s,2,16%s> grid %u tiles/wave %u", lv_name(p->bps, p->coder), nt ? "nt" : "plain",
+            gl8 ? ",glds" : "", g2.x, a.tpw);
+    BB_HIP(hipGetLastError());
+    return BB_OK;
+}
+
+// 4. the plain kernel (k_decode_flat): one workgroup of four waves per work item
+static int decode_flat_plain(const bb_decode_params *p, bb_flat_args &a, int om, uint64_t out_bytes, bool nt, hipStream_t st)
+{
+    const int seg_knob = g_tune_seg_tiles.load();
+    const uint64_t seg_plain = seg_knob ? (uint64_t)seg_knob : (p->bps == 8 ? 16u : (uint64_t)BB_SEG_TILES);
+    split_tiles(a, flat_ntiles(a), seg_plain, BB_WAVES_PER_BLOCK);
+    const uint64_t nwork = a.nfs * a.nseg;
+    a.perm = make_perm(nwork, out_bytes, BB_ORDER_FLAT);
+    const dim3 grid = capped_grid(nwork, BB_GRID_MAX);
+    launch_flat(p->bps, p->coder, om, nt, grid, st, a);
+    BB_NOTE("k_decode_flat<%d,%s,%d,%s> grid %u", p->bps, lv_name(p->bps, p->coder), om,
+            nt ? "nt" : "plain", grid.x);
     BB_HIP(hipGetLastError());
     return BB_OK;
 }
@@ -967,37 +1203,22 @@ int bb_decode_frames(const void *d_buf, size_t buf_nbytes,
     if (p->out_type != BB_OUT_F32)          // 16-bit output (or an unknown type: BB_EINVAL)
         return decode_half(d_buf, buf_nbytes, d_src, nframes, p, d_out, out_elems, stream);
     if (!coder_supported(p->coder, p->bps)) return BB_ENOTSUP;
-    if (nframes == 0) return BB_OK;
-    if (!d_buf || !d_out) return BB_EINVAL;
-    if (p->nslot < 1 || p->chunk < 1) return BB_EINVAL;
-    if (p->payload_nbytes == 0 || (p->payload_nbytes & 3)) return BB_EINVAL;
-    if (((uintptr_t)d_buf & 3) || ((uintptr_t)d_out & 15)) return BB_EINVAL;
+    if (nframes == 0) return BB_OK;         // (an empty float32 request is taken once its coder is: bbdecode.h)
+    int rc = decode_params_check(p);
+    if (rc) return rc;
     const uint64_t E = p->payload_nbytes * 8 / (uint64_t)p->bps;
     const uint64_t nfs = (uint64_t)nframes * (uint64_t)p->nslot;
-    uint32_t lchunk = 0;
-    int om = BB_OUT_FLAT;
-    if (p->nslot > 1) {
-        if (p->chunk & (p->chunk - 1)) return BB_ENOTSUP;   // VDIF nchan is 2^k
-        while ((1u << lchunk) < (uint32_t)p->chunk) ++lchunk;
-        if (E % (uint64_t)p->chunk) return BB_EINVAL;
-        om = (p->chunk % 4 == 0) ? BB_OUT_ROWS4 : BB_OUT_SCATTER;
-    }
-    if (out_elems < nfs * E) return BB_ERANGE;
-    if (!d_src) {
-        if ((p->src0 & 3) || (p->src_stride & 3) || p->src0 < 0 || p->src_stride < 0) return BB_EINVAL;
-        if (nfs && (uint64_t)p->src0 + (nfs - 1) * (uint64_t)p->src_stride + p->payload_nbytes > buf_nbytes)
-            return BB_ERANGE;
-    }
-    if (nfs == 0) return BB_OK;
-    int rc = ensure_init();
+    rc = decode_buffers_check(d_buf, buf_nbytes, d_src, nfs, p, d_out, out_elems);
+    if (rc) return rc;
+    const int om = p->nslot == 1 ? BB_OUT_FLAT : (p->chunk % 4 == 0) ? BB_OUT_ROWS4 : BB_OUT_SCATTER;
+    rc = ensure_init();
     if (rc) return rc;
 
-    const int lb = log2_bps(p->bps);
     bb_flat_args a;
     a.buf = (const uint8_t *)d_buf;
     a.src = d_src;
     a.out = d_out;
-    rc = device_levels(p->coder, lb, &a.tab);
+    rc = device_levels(p->coder, log2_bps(p->bps), &a.tab);
     if (rc) return rc;
     a.nfs = nfs;
     a.ndw = p->payload_nbytes / 4;
@@ -1006,7 +1227,7 @@ int bb_decode_frames(const void *d_buf, size_t buf_nbytes,
     a.src_stride = p->src_stride;
     a.nslot = (uint32_t)p->nslot;
     a.chunk = (uint32_t)p->chunk;
-    a.lchunk = lchunk;
+    a.lchunk = p->nslot > 1 ? ceil_log2((uint32_t)p->chunk) : 0;
     a.fill_re = p->fill_re;
     a.fill_im = p->fill_im;
     a.complex_data = p->complex_data;
@@ -1034,9 +1255,7 @@ int bb_decode_frames(const void *d_buf, size_t buf_nbytes,
     }
 #endif
 
-    const uint64_t ntiles = (a.ndw + 63) / 64;
     const uint64_t out_bytes = nfs * E * 4;
-    const int tb = g_tune_blocks.load();
 
     // 1. Thread interleave through the LDS gather (k_gather.h): narrow chunks
     // (a thread's sample is less than 128 bytes of output -- through the rows
@@ -1055,174 +1274,28 @@ int bb_decode_frames(const void *d_buf, size_t buf_nbytes,
     const bool gather_wide = om == BB_OUT_ROWS4
         && (gchunks == 32 ? (p->nslot <= 4 || p->chunk < 32 || big2) : p->chunk < gchunks);
     if ((om == BB_OUT_SCATTER || gather_wide) && d_src
-        && (size_t)p->nslot * 528 + 1024 + 64 <= 48 * 1024) {
-        bb_gather_args ga;
-        ga.within = nullptr; ga.nsel = 0; ga.mag_row = ga.mag_sel = 0;
-        ga.buf = a.buf; ga.src = d_src; ga.out = d_out; ga.tab = a.tab;
-        ga.nframes = nframes; ga.ndw = a.ndw;
-        ga.nslot = a.nslot; ga.chunk = a.chunk; ga.lchunk = a.lchunk;
-        ga.src_lim = a.src_lim;
-        // bytes staged per work item: 16 KiB, 4 KiB for 1-bit data whose items
-        // expand 32-fold (profiles/r01i_exp_interleave_gb.log); knob value 8192 = this default
-        size_t gbytes = (size_t)g_tune_gather_bytes.load();
-        if (gbytes == 8192) gbytes = p->bps == 1 ? 4096 : 16384;
-        uint32_t gt = (uint32_t)(gbytes / ((size_t)p->nslot * 256));
-        if (gt < 1) gt = 1;
-        if (gt > 32) gt = 32;
-        if ((uint64_t)gt > ntiles) gt = (uint32_t)ntiles;
-        ga.gtiles = gt;
-        ga.ngroup = (uint32_t)((ntiles + gt - 1) / gt);
-        ga.fill_re = a.fill_re; ga.fill_im = a.fill_im; ga.complex_data = a.complex_data;
-        {
-            const uint32_t rl = (uint32_t)p->nslot * (uint32_t)p->chunk;
-            ga.lrow = -1;
-            if ((rl & (rl - 1)) == 0) { ga.lrow = 0; while ((1u << ga.lrow) < rl) ++ga.lrow; }
-        }
-        ga.aligned = 1;
-        ga.glds = g_tune_gather_glds.load() == 1;
-        const size_t lds = ((size_t)p->nslot * (gt * 64 + 65) + 2 * p->nslot + 1) * 4 + 1024;
-        // persistent grid: a workgroup walks about five work items (8 KiB of
-        // payload each); one workgroup per item costs 15 %, a few thousand
-        // long-running ones 5-10 % (profiles/r01f_exp_gather*.log)
-        uint64_t gb = (uint64_t)nframes * ga.ngroup;
-        ga.perm = make_perm(gb, out_bytes, BB_ORDER_GATHER);
-        const uint64_t gcap = tb > 0 ? (uint64_t)tb : BB_GRID_CAP;
-        if (gb > gcap) gb = gcap;
-        if (gb > 0x7fffffffull) gb = 0x7fffffffull;
-        const dim3 gg((unsigned)gb);
-        launch_gather(p->bps, p->coder, nt, gg, lds, st, ga);
-        BB_NOTE("k_decode_gather<%d,%s,%s,%s> grid %u gtiles %u lds %zu", p->bps, lv_name(p->bps, p->coder),
-                nt ? "nt" : "plain", ga.lchunk >= 2 ? "wide" : "narrow", gg.x, ga.gtiles, lds);
-        BB_HIP(hipGetLastError());
-        return BB_OK;
-    }
+        && (size_t)p->nslot * 528 + 1024 + 64 <= 48 * 1024)
+        return decode_gather(p, a, out_bytes, nt, st);
 
-    if (om == BB_OUT_ROWS4) {
-        // 2. thread interleave with wide chunks: one wave per thread slot, all
-        // waves on the same (up to 8) tiles (k_decode_rows_pipe)
-        const int nw = p->nslot >= 8 ? 8 : (p->nslot >= 4 ? 4 : 2);
-        const uint64_t seg_max = (uint64_t)g_tune_rows_tiles.load();
-        a.nseg = (ntiles + seg_max - 1) / seg_max;
-        a.seg_tiles = (uint32_t)((ntiles + a.nseg - 1) / a.nseg);
-        a.tpw = a.seg_tiles;
-        const uint64_t sgroups = ((uint64_t)p->nslot + nw - 1) / nw;
-        uint64_t b2 = (uint64_t)nframes * a.nseg * sgroups;
-        a.perm = make_perm(b2, out_bytes, BB_ORDER_ROWS);
-        const uint64_t cap = tb > 0 ? (uint64_t)tb : BB_GRID_CAP;
-        if (b2 > cap) b2 = cap;
-        const dim3 g2((unsigned)b2);
-        launch_rows_pipe(p->bps, p->coder, nt, nw, g2, st, a);
-        BB_NOTE("k_decode_rows_pipe<%d,%s,%s,%d,8,aligned> grid %u", p->bps, lv_name(p->bps, p->coder),
-                nt ? "nt" : "plain", nw, g2.x);
-        BB_HIP(hipGetLastError());
-        return BB_OK;
-    }
+    // 2. thread interleave with wide chunks: one wave per thread slot, all
+    // waves on the same (up to 8) tiles (k_decode_rows_pipe)
+    if (om == BB_OUT_ROWS4)
+        return decode_rows_pipe(p, a, out_bytes, nt, st);
 
-    if (om == BB_OUT_FLAT && p->bps <= 4) {
-        // 3. contiguous 1-, 2- and 4-bit output: the byte table kernel (k_lut.h)
-        // with SHORT work items, one per workgroup -- 32 KiB of OUTPUT each: 2
-        // waves x 2 / 4 / 8 tiles for 1- / 2- / 4-bit samples, grid up to 2^23.
-        // +2-4 % over 2 x 8-12 tiles on 131072 persistent workgroups at every
-        // size from 2 to 8 GiB, for 8000-, 8192- and 10000-byte payloads
-        // (profiles/r02ao_exp_tpw_grid*.log): many small workgroups in flight
-        // overlap loads and stores better than a register pipeline, as for the
-        // 8-bit kernels.  1-bit 6.58 -> 6.86 TB/s against 4 tiles, 4-bit 5.28 ->
-        // 6.62 and +7 % over the plain kernel it used before
-        // (profiles/r02ar_exp_1bit_items.log, r02ar_exp_4bit_lut.log)
-        // 2-bit samples: k_decode_flat_lds (16-byte loads through LDS, at most 8 tiles
-        // per wave); 1- and 4-bit: k_decode_flat_lut -- profiles/r03j_exp_lds.log
-#if BB_EXP
-        if (p->bps == 2 && g_tune_burst.load() != 0 && p->payload_nbytes >= 256) {
-            // 3a. the loader-wave kernel (k_burst.h): items of up to one staging buffer
-            bb_burst_args b;
-            b.buf = a.buf; b.src = d_src; b.out = d_out; b.tab = a.tab;
-            b.nfs = nfs; b.pbytes = p->payload_nbytes;
-            b.buf_bytes = (uint32_t)g_tune_burst_bytes.load();
-            const uint64_t fst = (b.pbytes + 30) & ~15ull;
-            if (fst <= b.buf_bytes) {
-                b.nseg = 1; b.seg_bytes = 0; b.fstride = (uint32_t)fst;
-                uint64_t k = b.buf_bytes / fst;
-                if (k > BB_BURST_MAXK) k = BB_BURST_MAXK;
-                b.kpi = (uint32_t)k;
-            } else {
-                b.seg_bytes = (b.buf_bytes - 32) & ~255u;
-                b.nseg = (b.pbytes + b.seg_bytes - 1) / b.seg_bytes;
-                b.fstride = b.buf_bytes; b.kpi = 1;
-            }
-            b.magic = (uint32_t)((1ull << 32) / b.pbytes) + 1;
-            const uint64_t nwork = nfs * b.nseg;
-            b.nitems = (nwork + b.kpi - 1) / b.kpi;
-            b.period = (uint32_t)g_tune_burst_period.load();
-            b.src0 = a.src0; b.src_stride = a.src_stride;
-            b.fill_re = a.fill_re; b.fill_im = a.fill_im; b.complex_data = a.complex_data;
-            b.src_lim = a.src_lim;
-            b.perm = make_perm(b.nitems, out_bytes);
-            const int nst = g_tune_burst_waves.load();
-            const size_t ldsb = BB_BURST_HEAD + 2 * (size_t)b.buf_bytes;
-            uint64_t per_cu = (160 * 1024) / ldsb;
-            const uint64_t by_waves = 32 / (uint64_t)(nst + 1);
-            if (per_cu > by_waves) per_cu = by_waves;
-            if (per_cu < 1) per_cu = 1;
-            uint64_t gb = tb > 0 ? (uint64_t)tb : 256 * per_cu;
-            if (gb > b.nitems) gb = b.nitems;
-            const dim3 gg((unsigned)gb);
-            int brc;
-            if (nst == 3) brc = launch_flat_burst<3>(nt, gg, ldsb, st, b);
-            else if (nst == 7) brc = launch_flat_burst<7>(nt, gg, ldsb, st, b);
-            else brc = launch_flat_burst<15>(nt, gg, ldsb, st, b);
-            if (brc) return brc;
-            BB_NOTE("k_decode_flat_burst<2,%s,%d> grid %u pieces/item %u buffer %u period %u", nt ? "nt" : "plain", nst,
-                    gg.x, b.kpi, b.buf_bytes, b.period);
-            BB_HIP(hipGetLastError());
-            return BB_OK;
-        }
-#endif
-        bool lds = p->bps == 2 || p->bps == 4;
-#if BB_EXP
-        if (g_tune_variant.load() == 15 || (g_tune_variant.load() >= 19 && g_tune_variant.load() <= 25)) lds = true;        // A/B: force either kernel for every sample width
-        if (g_tune_variant.load() == 16) lds = false;
-#endif
-        // (2-bit through k_decode_flat_lds: 6 tiles per wave -- 0.851-0.859 of the peak with
-        // and without an index on three boxes, 4 tiles: 0.850-0.858 with, 0.837-0.848
-        // without; profiles/r04d_exp_glds3_box*.log.  Knob 0 = these defaults.)
-        const int lt_knob = g_tune_lut_tpw.load();
-        // (4-bit through k_decode_flat_lds: 4 tiles per wave; r04r_exp_glds5_box*.log)
-        int lut_tiles = lt_knob == 0 ? ((lds && p->bps == 2) ? 6 : (lds && p->bps == 4) ? 4 : 4 * p->bps / 2) : lt_knob * p->bps / 2;
-        lut_tiles = lut_tiles < 1 ? 1 : lut_tiles > (lds ? 8 : 16) ? (lds ? 8 : 16) : lut_tiles;
-        uint64_t nwv = 2;                                   // waves per workgroup
-#if BB_EXP
-        if (lds && p->bps == 2 && g_tune_variant.load() == 21) nwv = 4;     // A/B: 4 / 1 waves per workgroup
-        if (lds && p->bps == 2 && g_tune_variant.load() == 22) nwv = 1;
-#endif
-        const uint64_t seg_max = nwv * (uint64_t)lut_tiles;
-        a.nseg = (ntiles + seg_max - 1) / seg_max;
-        a.seg_tiles = (uint32_t)((ntiles + a.nseg - 1) / a.nseg);
-        a.tpw = (uint32_t)((a.seg_tiles + nwv - 1) / nwv);
-        uint64_t b2 = nfs * a.nseg;
-        a.perm = make_perm(b2, out_bytes, BB_ORDER_FLAT);
-        const uint64_t cap = tb > 0 ? (uint64_t)tb : (1ull << 23);
-        if (b2 > cap) b2 = cap;
-        const dim3 g2((unsigned)b2);
-        if (lds) {
-#if BB_EXP
-            if (p->bps == 1) launch_flat_lds<1>(nt, g2, st, a);
-            else
-#endif
-            if (p->bps == 4) launch_flat_lds<4>(nt, g2, st, a);
-            else launch_flat_lds<2>(nt, g2, st, a);
-            const char *gl = "";
-#if BB_EXP
-            if (p->bps != 1 && g_tune_variant.load() == 19) gl = ",regs";
-            if (p->bps == 1 && g_tune_variant.load() == 20) gl = ",glds";
-#endif
-            BB_NOTE("k_decode_flat_lds<%d,%s,2,8%s> grid %u tiles/wave %u", p->bps, nt ? "nt" : "plain", gl, g2.x, a.tpw);
-        } else {
-            launch_flat_lut(p->bps, nt, g2, st, a);
-            BB_NOTE("k_decode_flat_lut<%d,%s,2,16> grid %u tiles/wave %u", p->bps, nt ? "nt" : "plain", g2.x, a.tpw);
-        }
-        BB_HIP(hipGetLastError());
-        return BB_OK;
-    }
+    // 3. contiguous 1-, 2- and 4-bit output: the byte table kernel (k_lut.h)
+    // with SHORT work items, one per workgroup -- 32 KiB of OUTPUT each: 2
+    // waves x 2 / 4 / 8 tiles for 1- / 2- / 4-bit samples, grid up to 2^23.
+    // +2-4 % over 2 x 8-12 tiles on 131072 persistent workgroups at every
+    // size from 2 to 8 GiB, for 8000-, 8192- and 10000-byte payloads
+    // (profiles/r02ao_exp_tpw_grid*.log): many small workgroups in flight
+    // overlap loads and stores better than a register pipeline, as for the
+    // 8-bit kernels.  1-bit 6.58 -> 6.86 TB/s against 4 tiles, 4-bit 5.28 ->
+    // 6.62 and +7 % over the plain kernel it used before
+    // (profiles/r02ar_exp_1bit_items.log, r02ar_exp_4bit_lut.log)
+    // 2-bit samples: k_decode_flat_lds (16-byte loads through LDS, at most 8 tiles
+    // per wave); 1- and 4-bit: k_decode_flat_lut -- profiles/r03j_exp_lds.log
+    if (om == BB_OUT_FLAT && p->bps <= 4)
+        return decode_flat_lut(p, a, out_bytes, nt, st);
 
     // 3b. contiguous int8 output (DADA, GSB, GUPPI real; 20 % of the traffic is
     // reads): k_decode_flat_lds<8> with direct-to-LDS loads, 2 waves x 4 tiles = 8
@@ -1231,45 +1304,29 @@ int bb_decode_frames(const void *d_buf, size_t buf_nbytes,
     // r04c_exp_glds2.log); with 8 / 16 tiles per wave or register staging it
     // loses.  VDIF 8-bit frames (table levels) stay with the plain kernel up to
     // 20 GiB of payload: -6 % at 8 GiB, +3-4 % at 31 GiB (the switch below).
-    {
-        bool lds8 = om == BB_OUT_FLAT && p->bps == 8 && p->coder == BB_CODER_INT;
-        bool gl8 = true;
-        int t8 = 4;
-        // VDIF 8-bit frames (table levels), round 5: BY SIZE.  k_decode_flat_lds<8,LDS,glds> with 16
-        // tiles per wave against the plain kernel, 8032-byte frames (profiles/r05g_exp_vdif8_size.log):
-        // 0.5-12 GiB in: -0.1 .. -3.4 %; 16 GiB +0.4 %, 24 GiB +2.5 %, 31 GiB +4.1 % (0.791 -> 0.823 of
-        // the peak).  From 20 GiB of payload on it takes the staged kernel.
-        if (om == BB_OUT_FLAT && p->bps == 8 && p->coder != BB_CODER_INT
-            && nfs * (uint64_t)p->payload_nbytes >= ((uint64_t)g_tune_vdif8_lds_gib.load() << 30)) {
-            lds8 = true;
-            t8 = 16;
-        }
-#if BB_EXP
-        const int f8 = g_tune_flat8_lds.load();                 // 1: staged for every coder, knobs apply; 2: plain kernel
-        if (f8 == 1) {
-            lds8 = om == BB_OUT_FLAT && p->bps == 8;
-            t8 = (g_tune_lut_tpw.load() ? g_tune_lut_tpw.load() : 4) * 4;
-            t8 = t8 < 1 ? 1 : t8 > 16 ? 16 : t8;
-            gl8 = g_tune_variant.load() == 20;
-        } else if (f8 == 2) lds8 = false;
-#endif
-        if (lds8) {
-            const uint64_t seg_max = 2ull * (uint64_t)t8;
-            a.nseg = (ntiles + seg_max - 1) / seg_max;
-            a.seg_tiles = (uint32_t)((ntiles + a.nseg - 1) / a.nseg);
-            a.tpw = (a.seg_tiles + 1) / 2;
-            uint64_t b2 = nfs * a.nseg;
-            a.perm = make_perm(b2, out_bytes, BB_ORDER_FLAT);
-            const uint64_t cap = tb > 0 ? (uint64_t)tb : (1ull << 23);
-            if (b2 > cap) b2 = cap;
-            const dim3 g2((unsigned)b2);
-            launch_flat_lds8(p->coder, nt, gl8, g2, st, a);
-            BB_NOTE("k_decode_flat_lds<8,%s,%s,2,16%s> grid %u tiles/wave %u", lv_name(p->bps, p->coder), nt ? "nt" : "plain",
-                    gl8 ? ",glds" : "", g2.x, a.tpw);
-            BB_HIP(hipGetLastError());
-            return BB_OK;
-        }
+    bool lds8 = om == BB_OUT_FLAT && p->bps == 8 && p->coder == BB_CODER_INT;
+    bool gl8 = true;
+    int t8 = 4;
+    // VDIF 8-bit frames (table levels), round 5: BY SIZE.  k_decode_flat_lds<8,LDS,glds> with 16
+    // tiles per wave against the plain kernel, 8032-byte frames (profiles/r05g_exp_vdif8_size.log):
+    // 0.5-12 GiB in: -0.1 .. -3.4 %; 16 GiB +0.4 %, 24 GiB +2.5 %, 31 GiB +4.1 % (0.791 -> 0.823 of
+    // the peak).  From 20 GiB of payload on it takes the staged kernel.
+    if (om == BB_OUT_FLAT && p->bps == 8 && p->coder != BB_CODER_INT
+        && nfs * (uint64_t)p->payload_nbytes >= ((uint64_t)g_tune_vdif8_lds_gib.load() << 30)) {
+        lds8 = true;
+        t8 = 16;
     }
+#if BB_EXP
+    const int f8 = g_tune_flat8_lds.load();                 // 1: staged for every coder, knobs apply; 2: plain kernel
+    if (f8 == 1) {
+        lds8 = om == BB_OUT_FLAT && p->bps == 8;
+        t8 = (g_tune_lut_tpw.load() ? g_tune_lut_tpw.load() : 4) * 4;
+        t8 = t8 < 1 ? 1 : t8 > 16 ? 16 : t8;
+        gl8 = g_tune_variant.load() == 20;
+    } else if (f8 == 2) lds8 = false;
+#endif
+    if (lds8)
+        return decode_flat_lds8(p, a, t8, gl8, out_bytes, nt, st);
 
     // 4. the plain kernel (k_decode_flat): one workgroup of four waves per work
     // item, loads and stores in the same iteration, uncapped grid.  8-bit
@@ -1280,27 +1337,7 @@ int bb_decode_frames(const void *d_buf, size_t buf_nbytes,
     // KiB out) instead of 32: +7 % at 8 GiB, +0-3.5 % at 31 GiB
     // (profiles/r02ba_exp_int8_seg.log).  Also the general fallback: thread
     // interleave without an index, or with more slots than the gather stages.
-    {
-        const int seg_knob = g_tune_seg_tiles.load();
-        const uint64_t seg_plain = seg_knob ? (uint64_t)seg_knob : (p->bps == 8 ? 16u : (uint64_t)BB_SEG_TILES);
-        a.nseg = (ntiles + seg_plain - 1) / seg_plain;
-        // split a frame-slot's tiles evenly over its work items and a work item's
-        // tiles evenly over the four waves (a 10000-byte Mark 5B payload is 40
-        // tiles: 2 items x 20 tiles x 5 per wave, not 32 + 8)
-        a.seg_tiles = (uint32_t)((ntiles + a.nseg - 1) / a.nseg);
-        a.tpw = (a.seg_tiles + BB_WAVES_PER_BLOCK - 1) / BB_WAVES_PER_BLOCK;
-        const uint64_t nwork = nfs * a.nseg;
-        a.perm = make_perm(nwork, out_bytes, BB_ORDER_FLAT);
-        uint64_t blocks = nwork;
-        if (tb > 0 && blocks > (uint64_t)tb) blocks = (uint64_t)tb;
-        if (blocks > 0x7fffffffull) blocks = 0x7fffffffull;
-        const dim3 grid((unsigned)blocks);
-        launch_flat(p->bps, p->coder, om, nt, grid, st, a);
-        BB_NOTE("k_decode_flat<%d,%s,%d,%s> grid %u", p->bps, lv_name(p->bps, p->coder), om,
-                nt ? "nt" : "plain", grid.x);
-        BB_HIP(hipGetLastError());
-        return BB_OK;
-    }
+    return decode_flat_plain(p, a, om, out_bytes, nt, st);
 }
 
 // Argument checks and work geometry of bb_decode_frames_select, shared with
@@ -1316,8 +1353,7 @@ static int select_geometry(const bb_decode_params *p, int nwithin, select_geom *
     if (p->nslot < 1 || p->chunk < 1 || nwithin < 1 || nwithin > 4096) return BB_EINVAL;
     if (p->payload_nbytes == 0 || (p->payload_nbytes & 3)) return BB_EINVAL;
     if (p->chunk & (p->chunk - 1)) return BB_ENOTSUP;
-    uint32_t lchunk = 0;
-    while ((1u << lchunk) < (uint32_t)p->chunk) ++lchunk;
+    const uint32_t lchunk = ceil_log2((uint32_t)p->chunk);
     const uint64_t E = p->payload_nbytes * 8 / (uint64_t)p->bps;
     if (E % (uint64_t)p->chunk) return BB_EINVAL;
     const uint64_t ntiles = (p->payload_nbytes / 4 + 63) / 64;
@@ -1346,9 +1382,9 @@ int bb_touch(const void *d_buf, size_t nbytes, void *stream)
     const uintptr_t lo = ((uintptr_t)d_buf + 15) & ~(uintptr_t)15, hi = ((uintptr_t)d_buf + nbytes) & ~(uintptr_t)15;
     if (hi <= lo) return BB_OK;
     const uint64_t nchunk = (uint64_t)(hi - lo) / 16;
-    const uint64_t blocks = (nchunk + BB_BLOCK - 1) / BB_BLOCK;
-    if (blocks > 0x7fffffffull) return BB_ERANGE;
-    hipLaunchKernelGGL(k_touch, dim3((unsigned)blocks), dim3(BB_BLOCK), 0, (hipStream_t)stream,
+    dim3 grid;
+    if (int rc = record_grid(nchunk, BB_BLOCK, &grid)) return rc;
+    hipLaunchKernelGGL(k_touch, grid, dim3(BB_BLOCK), 0, (hipStream_t)stream,
                        (const bb_u4 *)lo, nchunk, (uint32_t *)nullptr);
     BB_HIP(hipGetLastError());
     return BB_OK;
@@ -1378,6 +1414,27 @@ static int touch_window(const void *d_buf, size_t nbytes, void *stream)
     return bb_touch(d_buf, nbytes, stream);
 }
 
+// What a window call does before its scan: the argument rules the three formats share, the
+// output check where the decode takes a bb_decode_params (`dec`; null for Mark 4), the stream
+// of the scan / index / verification launches (`*ss`) and the pre-read.
+static int window_begin(const void *d_buf, size_t nbytes, bool have_blocks, const bb_decode_params *dec, int nwithin,
+                        void *verified, void *scan_stream, void *stream, void **ss)
+{
+    if (!have_blocks) return BB_EINVAL;
+    if (scan_stream && !verified) return BB_EINVAL;        // (the decode's stream waits for that event)
+    if (dec) { const int orc = window_out_check(dec, nwithin); if (orc != BB_OK) return orc; }
+    *ss = scan_stream ? scan_stream : stream;
+    return touch_window(d_buf, nbytes, stream);
+}
+
+// ... and behind its verification launch: the event is recorded, the decode's stream waits for it
+static int window_verified(void *verified, void *scan_stream, void *ss, void *stream)
+{
+    if (verified) BB_HIP(hipEventRecord((hipEvent_t)verified, (hipStream_t)ss));
+    if (scan_stream) BB_HIP(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)verified, 0));
+    return BB_OK;
+}
+
 int bb_vdif_read_window(const void *d_buf, size_t nbytes,
                         const bb_vdif_scan_params *scan, size_t nframes,
                         const int16_t *d_thread_slot, size_t nsets,
@@ -1388,21 +1445,19 @@ int bb_vdif_read_window(const void *d_buf, size_t nbytes,
                         uint32_t recs_per_index, size_t nstrict, uint32_t *d_nbad,
                         void *verified, void *scan_stream, void *stream)
 {
-    if (!scan || !dec || !d_src || dec->nslot < 1) return BB_EINVAL;
-    if (scan_stream && !verified) return BB_EINVAL;        // (the decode's stream waits for that event)
-    { const int orc = window_out_check(dec, nwithin); if (orc != BB_OK) return orc; }
-    void *ss = scan_stream ? scan_stream : stream;
-    { const int trc = touch_window(d_buf, nbytes, stream); if (trc != BB_OK) return trc; }
+    void *ss;
+    int rc = window_begin(d_buf, nbytes, scan && dec && d_src && dec->nslot >= 1, dec, nwithin, verified, scan_stream, stream, &ss);
+    if (rc != BB_OK) return rc;
     // three launches: scan (which also pre-sets the index to -1), index + verification, decode
     bb_vdif_scan_params sp = *scan;
     sp.set_nframes = (int32_t)recs_per_index;               // frame sets in file order (bbdecode.h)
-    int rc = vdif_scan_impl(d_buf, nbytes, &sp, d_recs, nframes, d_src, nsets * (size_t)dec->nslot, ss);
+    rc = vdif_scan_impl(d_buf, nbytes, &sp, d_recs, nframes, d_src, nsets * (size_t)dec->nslot, ss);
     if (rc != BB_OK) return rc;
     rc = index_verify(d_recs, nframes, d_thread_slot, dec->nslot, d_src, nsets, true, recs_per_index ? recs_per_index : 1,
                       nstrict, d_nbad, ss);
     if (rc != BB_OK) return rc;
-    if (verified) BB_HIP(hipEventRecord((hipEvent_t)verified, (hipStream_t)ss));
-    if (scan_stream) BB_HIP(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)verified, 0));
+    rc = window_verified(verified, scan_stream, ss, stream);
+    if (rc != BB_OK) return rc;
     if (nwithin > 0)
         return bb_decode_frames_select(d_buf, nbytes, d_src, nsets, dec, d_within, nwithin, d_out, out_elems, stream);
     return bb_decode_frames(d_buf, nbytes, d_src, nsets, dec, d_out, out_elems, stream);
@@ -1416,17 +1471,15 @@ int bb_mark5b_read_window(const void *d_buf, size_t nbytes,
                           float *d_out, size_t out_elems,
                           size_t nstrict, uint32_t *d_nbad, void *verified, void *scan_stream, void *stream)
 {
-    if (!scan || !dec) return BB_EINVAL;
-    if (scan_stream && !verified) return BB_EINVAL;
-    { const int orc = window_out_check(dec, nwithin); if (orc != BB_OK) return orc; }
-    void *ss = scan_stream ? scan_stream : stream;
-    { const int trc = touch_window(d_buf, nbytes, stream); if (trc != BB_OK) return trc; }
-    int rc = bb_mark5b_scan(d_buf, nbytes, scan, d_recs, nframes, ss);
+    void *ss;
+    int rc = window_begin(d_buf, nbytes, scan && dec, dec, nwithin, verified, scan_stream, stream, &ss);
+    if (rc != BB_OK) return rc;
+    rc = bb_mark5b_scan(d_buf, nbytes, scan, d_recs, nframes, ss);
     if (rc != BB_OK) return rc;
     rc = index_verify(d_recs, nframes, nullptr, 1, d_src, n, false, 1, nstrict, d_nbad, ss);
     if (rc != BB_OK) return rc;
-    if (verified) BB_HIP(hipEventRecord((hipEvent_t)verified, (hipStream_t)ss));
-    if (scan_stream) BB_HIP(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)verified, 0));
+    rc = window_verified(verified, scan_stream, ss, stream);
+    if (rc != BB_OK) return rc;
     if (nwithin > 0)
         return bb_decode_frames_select(d_buf, nbytes, d_src, n, dec, d_within, nwithin, d_out, out_elems, stream);
     return bb_decode_frames(d_buf, nbytes, d_src, n, dec, d_out, out_elems, stream);
@@ -1439,16 +1492,15 @@ int bb_mark4_read_window(const void *d_buf, size_t nbytes,
                          float *d_out, size_t out_elems,
                          size_t nstrict, uint32_t *d_nbad, void *verified, void *scan_stream, void *stream)
 {
-    if (!scan || !dec) return BB_EINVAL;
-    if (scan_stream && !verified) return BB_EINVAL;
-    void *ss = scan_stream ? scan_stream : stream;
-    { const int trc = touch_window(d_buf, nbytes, stream); if (trc != BB_OK) return trc; }
-    int rc = bb_mark4_scan(d_buf, nbytes, scan, d_recs, nframes, ss);
+    void *ss;
+    int rc = window_begin(d_buf, nbytes, scan && dec, nullptr, 0, verified, scan_stream, stream, &ss);
+    if (rc != BB_OK) return rc;
+    rc = bb_mark4_scan(d_buf, nbytes, scan, d_recs, nframes, ss);
     if (rc != BB_OK) return rc;
     rc = index_verify(d_recs, nframes, nullptr, 1, d_src, n, false, 1, nstrict, d_nbad, ss);
     if (rc != BB_OK) return rc;
-    if (verified) BB_HIP(hipEventRecord((hipEvent_t)verified, (hipStream_t)ss));
-    if (scan_stream) BB_HIP(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)verified, 0));
+    rc = window_verified(verified, scan_stream, ss, stream);
+    if (rc != BB_OK) return rc;
     if (nout > 0)
         return bb_decode_mark4_select(d_buf, nbytes, d_src, n, dec, nout, d_out, out_elems, stream);
     return bb_decode_mark4(d_buf, nbytes, d_src, n, dec, d_out, out_elems, stream);
@@ -1471,12 +1523,13 @@ int bb_copy_frames(const void *d_buf, size_t buf_nbytes, size_t nframes, uint64_
 {
     if (nframes == 0 || nbytes_per_frame == 0) { BB_NOTE("none"); return BB_OK; }
     if (!d_buf || !d_out) return BB_EINVAL;
-    if ((nbytes_per_frame & 3) || (src0 & 3) || (src_stride & 3) || src0 < 0 || src_stride < 0
-        || (reinterpret_cast<uintptr_t>(d_buf) & 3) || (reinterpret_cast<uintptr_t>(d_out) & 3)) return BB_EINVAL;
-    if (nframes > 1 && (uint64_t)src_stride < nbytes_per_frame && src_stride != 0) return BB_EINVAL;
+    if ((nbytes_per_frame & 3) || (reinterpret_cast<uintptr_t>(d_buf) & 3) || (reinterpret_cast<uintptr_t>(d_out) & 3))
+        return BB_EINVAL;
+    if (nframes > 1 && src_stride > 0 && (uint64_t)src_stride < nbytes_per_frame) return BB_EINVAL;
     if ((uint64_t)nframes > (~0ull) / nbytes_per_frame || (uint64_t)nframes * nbytes_per_frame > out_nbytes) return BB_ERANGE;
-    if ((uint64_t)src0 + (uint64_t)(nframes - 1) * (uint64_t)src_stride + nbytes_per_frame > buf_nbytes) return BB_ERANGE;
-    int rc = ensure_init();
+    int rc = fixed_stride_check(src0, src_stride, 4, nframes, nbytes_per_frame, buf_nbytes);
+    if (rc) return rc;
+    rc = ensure_init();
     if (rc) return rc;
     bb_copy_args a;
     a.buf = (const uint8_t *)d_buf; a.out = (uint8_t *)d_out;
@@ -1493,11 +1546,7 @@ int bb_copy_frames(const void *d_buf, size_t buf_nbytes, size_t nframes, uint64_
     a.perm = make_perm(nwork, (uint64_t)nframes * nbytes_per_frame);
     const bool v16 = !((reinterpret_cast<uintptr_t>(d_buf) | reinterpret_cast<uintptr_t>(d_out) | (uint64_t)src0
                         | (uint64_t)src_stride | nbytes_per_frame) & 15);
-    const int tb = g_tune_blocks.load();
-    uint64_t blocks = nwork;
-    const uint64_t cap = tb > 0 ? (uint64_t)tb : (1ull << 23);
-    if (blocks > cap) blocks = cap;
-    const dim3 grid((unsigned)blocks);
+    const dim3 grid = capped_grid(nwork, BB_GRID_SHORT_ITEMS);
     hipStream_t st = (hipStream_t)stream;
     const bool nt = tune_nt();
     with_nt(nt, [&](auto NT) {
@@ -1541,19 +1590,11 @@ int bb_decode_frames_select(const void *d_buf, size_t buf_nbytes,
     if (out_elems < (uint64_t)nframes * R * (uint64_t)p->nslot * (uint64_t)nwithin) return BB_ERANGE;
     rc = ensure_init();
     if (rc) return rc;
-    const int lb = log2_bps(p->bps);
-    bb_gather_args ga;
-    ga.buf = (const uint8_t *)d_buf; ga.src = d_src; ga.out = d_out;
-    rc = device_levels(p->coder, lb, &ga.tab);
+    const float *tab = nullptr;
+    rc = device_levels(p->coder, log2_bps(p->bps), &tab);
     if (rc) return rc;
-    ga.nframes = nframes; ga.ndw = p->payload_nbytes / 4;
-    ga.nslot = (uint32_t)p->nslot; ga.chunk = (uint32_t)p->chunk; ga.lchunk = lchunk;
-    ga.src_lim = src_limit(buf_nbytes, p->payload_nbytes);
-    ga.gtiles = gt;
-    ga.ngroup = (uint32_t)((ntiles + gt - 1) / gt);
-    ga.fill_re = p->fill_re; ga.fill_im = p->fill_im; ga.complex_data = p->complex_data;
-    ga.lrow = -1;
-    ga.aligned = 1;
+    bb_gather_args ga = gather_args((const uint8_t *)d_buf, d_src, d_out, tab, nframes, p, lchunk,
+                                    src_limit(buf_nbytes, p->payload_nbytes), gt, ntiles);
     ga.glds = g_tune_gather_glds.load() != 0;
     ga.within = d_within; ga.nsel = (uint32_t)nwithin;
     {
@@ -1587,22 +1628,18 @@ int bb_decode_frames_select(const void *d_buf, size_t buf_nbytes,
                 pa.buf = ga.buf; pa.src = d_src; pa.out = d_out; pa.tab = ga.tab; pa.within = d_within;
                 pa.nframes = nframes; pa.pbytes = p->payload_nbytes; pa.src_lim = ga.src_lim;
                 pa.nslot = (uint32_t)p->nslot; pa.nsel = (uint32_t)nwithin;
-                pa.lrowlen = 0;
-                while ((1ull << pa.lrowlen) < rowlen) ++pa.lrowlen;
+                pa.lrowlen = ceil_log2(rowlen);
                 pa.rowbytes = rowbytes; pa.sb = sb;
                 pa.nitem = (uint32_t)((p->payload_nbytes + sb - 1) / sb);
                 pa.pitch = sb + 80;                          // 16 bytes of misalignment + a bank skew between the slots' rows
                 pa.fill_re = p->fill_re; pa.fill_im = p->fill_im; pa.complex_data = p->complex_data;
                 const uint64_t nwork = (uint64_t)nframes * pa.nitem;
                 pa.perm = make_perm(nwork, (uint64_t)nframes * R * rowlen * 4);
-                uint64_t gbp = (nwork + BB_PICK_NW - 1) / BB_PICK_NW;
-                const int tbp = g_tune_blocks.load();
-                const uint64_t capp = tbp > 0 ? (uint64_t)tbp : (BB_GRID_CAP << 3);
-                if (gbp > capp) gbp = capp;
+                const dim3 gp = capped_grid((nwork + BB_PICK_NW - 1) / BB_PICK_NW, BB_GRID_CAP << 3);
                 const size_t ldsp = (size_t)BB_PICK_NW * pa.nslot * pa.pitch;
-                launch_pick(p->bps, p->coder, tune_nt(), dim3((unsigned)gbp), ldsp, (hipStream_t)stream, pa);
+                launch_pick(p->bps, p->coder, tune_nt(), gp, ldsp, (hipStream_t)stream, pa);
                 BB_NOTE("k_decode_pick<%d,%s,%s,%d> grid %u items of %u B x %u slots, select %d of %d", p->bps,
-                        lv_name(p->bps, p->coder), tune_nt() ? "nt" : "plain", BB_PICK_NW, (unsigned)gbp, sb, pa.nslot,
+                        lv_name(p->bps, p->coder), tune_nt() ? "nt" : "plain", BB_PICK_NW, gp.x, sb, pa.nslot,
                         nwithin, p->chunk);
                 BB_HIP(hipGetLastError());
                 return BB_OK;
@@ -1610,12 +1647,8 @@ int bb_decode_frames_select(const void *d_buf, size_t buf_nbytes,
         }
     }
     const size_t lds = g.lds;
-    uint64_t gb = (uint64_t)nframes * ga.ngroup;
-    ga.perm = make_perm(gb, (uint64_t)nframes * R * p->nslot * nwithin * 4);
-    const int tb = g_tune_blocks.load();
-    const uint64_t gcap = tb > 0 ? (uint64_t)tb : BB_GRID_CAP;
-    if (gb > gcap) gb = gcap;
-    const dim3 gg((unsigned)gb);
+    ga.perm = make_perm((uint64_t)nframes * ga.ngroup, (uint64_t)nframes * R * p->nslot * nwithin * 4);
+    const dim3 gg = capped_grid((uint64_t)nframes * ga.ngroup, BB_GRID_CAP);
     hipStream_t st = (hipStream_t)stream;
     const bool nt = tune_nt();
     // float4 stores when every work item's output starts on a 16-byte boundary
@@ -1640,10 +1673,9 @@ static int mark4_scan_impl(const void *d_buf, size_t nbytes, const bb_mark4_scan
     if (p->ntrack != 16 && p->ntrack != 32 && p->ntrack != 64) return BB_ENOTSUP;
     if ((!d_offsets && (p->first_offset & (p->ntrack / 8 - 1))) || ((uintptr_t)d_buf & 7)) return BB_EINVAL;
     if (p->frame_qms < 0) return BB_EINVAL;
-    if (nframes == 0) return BB_OK;
-    const uint64_t blocks = ((uint64_t)nframes + BB_WAVES_PER_BLOCK - 1) / BB_WAVES_PER_BLOCK;
-    if (blocks > 0x7fffffffull) return BB_ERANGE;
-    const dim3 grid((unsigned)blocks), block(BB_BLOCK);
+    dim3 grid;                                          // (a wave per frame)
+    if (int rc = record_grid(nframes, BB_WAVES_PER_BLOCK, &grid)) return rc;
+    const dim3 block(BB_BLOCK);
     hipStream_t st = (hipStream_t)stream;
     const uint8_t *b = (const uint8_t *)d_buf;
     switch (p->ntrack) {
@@ -1675,10 +1707,7 @@ int bb_mark4_locate(const void *d_buf, size_t nbytes, int ntrack, int64_t *d_off
     if (ntrack != 16 && ntrack != 32 && ntrack != 64) return BB_ENOTSUP;
     if ((uintptr_t)d_buf & 15) return BB_EINVAL;           // 16-byte loads (bb_locate_sweep)
     if (nbytes < (size_t)ntrack * 2500) return BB_OK;
-    uint64_t blocks = (nbytes / 16 + BB_BLOCK * BB_LOCATE_U - 1) / (BB_BLOCK * BB_LOCATE_U);   // BB_LOCATE_U x 16 bytes per lane and iteration
-    if (blocks > (g_tune_blocks.load() > 0 ? (uint64_t)g_tune_blocks.load() : BB_LOCATE_GRID)) blocks = g_tune_blocks.load() > 0 ? (uint64_t)g_tune_blocks.load() : BB_LOCATE_GRID;
-    if (blocks == 0) blocks = 1;
-    const dim3 grid((unsigned)blocks), block(BB_BLOCK);
+    const dim3 grid = locate_grid(nbytes), block(BB_BLOCK);
     hipStream_t st = (hipStream_t)stream;
     const uint8_t *b = (const uint8_t *)d_buf;
     switch (ntrack) {
@@ -1697,9 +1726,9 @@ int bb_mark4_header_crc(const void *d_buf, size_t nbytes, int ntrack, const int6
     if (!d_buf || !d_bad_tracks) return BB_EINVAL;
     if (ntrack != 16 && ntrack != 32 && ntrack != 64) return BB_ENOTSUP;
     if (!d_offsets && first_offset < 0) return BB_EINVAL;
-    const uint64_t blocks = ((uint64_t)nframes + BB_BLOCK - 1) / BB_BLOCK;
-    if (blocks > 0x7fffffffull) return BB_ERANGE;
-    const dim3 grid((unsigned)blocks), block(BB_BLOCK);
+    dim3 grid;
+    if (int rc = record_grid(nframes, BB_BLOCK, &grid)) return rc;
+    const dim3 block(BB_BLOCK);
     hipStream_t st = (hipStream_t)stream;
     const uint8_t *b = (const uint8_t *)d_buf;
     switch (ntrack) {
@@ -1758,11 +1787,7 @@ static int m4_decode(const void *d_buf, size_t buf_nbytes, const int64_t *d_src,
     a.nframes = nframes;
     a.nwords = p->nwords;
     a.fill_words = p->fill_words;
-    const uint64_t ntiles = (p->nwords + 63) / 64;
-    const uint64_t m4_seg = (uint64_t)BB_WAVES_PER_BLOCK * (uint64_t)g_tune_m4_tiles.load();
-    a.nseg = (ntiles + m4_seg - 1) / m4_seg;
-    a.seg_tiles = (uint32_t)((ntiles + a.nseg - 1) / a.nseg);
-    a.tpw = (a.seg_tiles + BB_WAVES_PER_BLOCK - 1) / BB_WAVES_PER_BLOCK;
+    split_tiles(a, (p->nwords + 63) / 64, (uint64_t)BB_WAVES_PER_BLOCK * (uint64_t)g_tune_m4_tiles.load(), BB_WAVES_PER_BLOCK);
     a.src0 = p->src0;
     a.src_stride = p->src_stride;
     memset(a.sign_bit, 0, sizeof(a.sign_bit));
@@ -1773,18 +1798,15 @@ static int m4_decode(const void *d_buf, size_t buf_nbytes, const int64_t *d_src,
     a.hi = h_levels[BB_CODER_VDIF][1][3];
     // (the unit's size in bytes is the same before and after widening)
     a.src_lim = src_limit(buf_nbytes, p_in->nwords * ((uint64_t)p_in->ntrack / 8));
-    uint64_t blocks = (uint64_t)nframes * a.nseg;
+    const uint64_t blocks = (uint64_t)nframes * a.nseg;
     a.perm = make_perm(blocks, (uint64_t)nframes * E * 4);
     hipStream_t st = (hipStream_t)stream;
     const bool nt = tune_nt();
     const dim3 block(BB_BLOCK);
     if (!select) {
-        const int tb = g_tune_blocks.load();
         // (one work item per workgroup up to 2^23: +1 % over 131072 persistent
         // workgroups at 8 GiB, equal at 2 GiB -- profiles/r02ao_exp_short_items.log)
-        const uint64_t cap = tb > 0 ? (uint64_t)tb : (1ull << 23);
-        if (blocks > cap) blocks = cap;
-        const dim3 grid((unsigned)blocks);
+        const dim3 grid = capped_grid(blocks, BB_GRID_SHORT_ITEMS);
 #define BB_M4(N) with_nt(nt, [&](auto NT) { \
             hipLaunchKernelGGL((k_decode_mark4<N, decltype(NT)::value>), grid, block, 0, st, a); })
         bool m4lds = false;
@@ -1805,8 +1827,8 @@ static int m4_decode(const void *d_buf, size_t buf_nbytes, const int64_t *d_src,
         BB_NOTE("k_decode_mark4%s<%d,%s> grid %u%s", m4lds ? "_lds" : "", p->ntrack, nt ? "nt" : "plain", grid.x,
                 p == &wide ? " (narrow words as 64-bit super-words)" : "");
     } else {
-        if (blocks > (1ull << 30)) blocks = 1ull << 30;     // no pipeline to fill: one work item per workgroup
-        const dim3 grid((unsigned)blocks);
+        // no pipeline to fill: one work item per workgroup, whatever BB_TUNE_BLOCKS says
+        const dim3 grid((unsigned)(blocks < (1ull << 30) ? blocks : 1ull << 30));
         // float4 stores need every unit to start on a 16-byte boundary
         const bool v4 = (E % 4 == 0) && (((uintptr_t)d_out & 15) == 0);
 #define BB_M4S(N) with_nt(nt, [&](auto NT) { \
@@ -1839,13 +1861,7 @@ static int m4_check(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, 
     for (int j = 0; j < nout; ++j)
         if (p->sign_bit[j] >= p->ntrack || p->mag_bit[j] >= p->ntrack) return BB_EINVAL;
     if (out_elems < (uint64_t)nframes * p->nwords * (uint64_t)nout) return BB_ERANGE;
-    if (!d_src) {
-        if (p->src0 < 0 || p->src_stride < 0 || (p->src0 % (int64_t)wbytes) || (p->src_stride % (int64_t)wbytes))
-            return BB_EINVAL;
-        if ((uint64_t)p->src0 + ((uint64_t)nframes - 1) * (uint64_t)p->src_stride + p->nwords * wbytes > buf_nbytes)
-            return BB_ERANGE;
-    }
-    return BB_OK;
+    return d_src ? BB_OK : fixed_stride_check(p->src0, p->src_stride, wbytes, nframes, p->nwords * wbytes, buf_nbytes);
 }
 
 int bb_decode_mark4(const void *d_buf, size_t buf_nbytes,
@@ -1909,9 +1925,8 @@ int bb_decode_i8_tiled(const void *d_buf, size_t buf_nbytes,
                     : p->layout == BB_LAYOUT_MKBF ? cut * 256 : cut * (uint64_t)p->npol) * 2;
     }
     if (!d_src) {
-        if (p->src0 < 0 || p->src_stride < 0 || (p->src0 & 1) || (p->src_stride & 1)) return BB_EINVAL;
-        if ((uint64_t)p->src0 + ((uint64_t)nframes - 1) * (uint64_t)p->src_stride + payload > buf_nbytes)
-            return BB_ERANGE;
+        const int rc = fixed_stride_check(p->src0, p->src_stride, 2, nframes, payload, buf_nbytes);
+        if (rc) return rc;
     }
     bb_tiled_args a;
     a.buf = (const uint8_t *)d_buf;
@@ -1938,7 +1953,6 @@ int bb_decode_i8_tiled(const void *d_buf, size_t buf_nbytes,
     }
     hipStream_t st = (hipStream_t)stream;
     const bool nt = tune_nt();
-    const int tb = g_tune_blocks.load();
     // Fast form (k_xpose.h) for the common geometry: every input run 16-byte
     // aligned, at least 8 channels (a selection: 2).  Fixed stride only (offsets from an index
     // cannot be checked for alignment here).
@@ -1974,11 +1988,9 @@ int bb_decode_i8_tiled(const void *d_buf, size_t buf_nbytes,
             b.magic_ppt = (uint32_t)((1ull << 32) / ppt) + 1;
             b.magic_half = (uint32_t)((1ull << 32) / halfp) + 1;
             b.fill_re = p->fill_re; b.fill_im = p->fill_im;
-            uint64_t blocks = (uint64_t)nframes * ntt;
+            const uint64_t blocks = (uint64_t)nframes * ntt;
             b.perm = make_perm(blocks, (uint64_t)nframes * (p->t_hi - p->t_lo) * rowlen * 4);
-            const uint64_t cap = tb > 0 ? (uint64_t)tb : 0x7fffffffull;
-            if (blocks > cap) blocks = cap;
-            const dim3 grid((unsigned)blocks), block(BB_BLOCK);
+            const dim3 grid = capped_grid(blocks, BB_GRID_MAX), block(BB_BLOCK);
             with_nt(nt, [&](auto NT) {
                 constexpr bool N = decltype(NT)::value;
                 hipLaunchKernelGGL((k_decode_i8_tf_pick<N>), grid, block, 0, st, b);
@@ -2012,7 +2024,7 @@ int bb_decode_i8_tiled(const void *d_buf, size_t buf_nbytes,
             if (ntt > 0xffffffffull) return BB_ERANGE;
             a.ntt = (uint32_t)ntt; a.nct = (uint32_t)nct;
             a.tt = (uint32_t)(rt / npd); a.tc = (uint32_t)xtc; a.tcp = 2 * ((uint32_t)xtc + 1);
-            uint64_t blocks = (uint64_t)nframes * ntt * nct;
+            const uint64_t blocks = (uint64_t)nframes * ntt * nct;
             a.perm = make_perm(blocks, (uint64_t)nframes * (p->t_hi - p->t_lo) * rowlen * 4, BB_ORDER_TILED);
             // one tile per workgroup: with 20 % of the traffic being reads the
             // dispatcher overlaps loads and stores of many small workgroups
@@ -2020,9 +2032,7 @@ int bb_decode_i8_tiled(const void *d_buf, size_t buf_nbytes,
             // profiles/r02g_exp_i8_grid.log: 5.16-5.31 TB/s with 131072
             // workgroups, 5.62-5.66 with one per tile; the flat int8 kernel
             // behaves the same way)
-            const uint64_t cap = tb > 0 ? (uint64_t)tb : 0x7fffffffull;
-            if (blocks > cap) blocks = cap;
-            const dim3 grid((unsigned)blocks), block(BB_BLOCK);
+            const dim3 grid = capped_grid(blocks, BB_GRID_MAX), block(BB_BLOCK);
 #define BB_XP1(L, R) \
                 if (xtc == 8)        hipLaunchKernelGGL((k_decode_i8_xpose<L, N, R, 8>), grid, block, 0, st, a); \
                 else if (xtc == 16)  hipLaunchKernelGGL((k_decode_i8_xpose<L, N, R, 16>), grid, block, 0, st, a); \
@@ -2082,11 +2092,9 @@ int bb_decode_i8_tiled(const void *d_buf, size_t buf_nbytes,
     a.ntt = (uint32_t)ntt;
     a.nct = (uint32_t)nct;
     if (lds > 64 * 1024) return BB_ENOTSUP;
-    uint64_t blocks = (uint64_t)nframes * ntt * nct;
+    const uint64_t blocks = (uint64_t)nframes * ntt * nct;
     a.perm = make_perm(blocks, (uint64_t)nframes * rows * rowlen * 4, BB_ORDER_TILED);
-    if (tb > 0 && blocks > (uint64_t)tb) blocks = (uint64_t)tb;
-    if (blocks > 0x7fffffffull) blocks = 0x7fffffffull;
-    const dim3 grid((unsigned)blocks), block(BB_BLOCK);
+    const dim3 grid = capped_grid(blocks, BB_GRID_MAX), block(BB_BLOCK);
 #define BB_TL(L) with_nt(nt, [&](auto NT) { hipLaunchKernelGGL((k_decode_i8_tiled<L, decltype(NT)::value>), grid, block, lds, st, a); })
 #define BB_TS(L) with_nt(nt, [&](auto NT) { hipLaunchKernelGGL((k_decode_i8_stage<L, decltype(NT)::value>), grid, block, lds, st, a); })
     switch (p->layout) {
@@ -2122,15 +2130,10 @@ int bb_encode_flat(const float *d_in, size_t nelem, int coder, int bps,
     const bool direct = g_tune_encode_direct.load() != 0;
     const int eruns = (direct && bps == 2) ? 1
                     : (bps == 4 || BB_EXP) ? (eknob ? eknob : (bps == 4 ? 2 : 1)) : 1;
-    uint64_t blocks = (nquad / 256 / eruns + 3) / 4 + 1;  // RUNS 256-quad runs per wave
     // one run per wave and as many workgroups as that takes: the encoder is a
     // streaming read without a software pipeline, the dispatcher overlaps it
     // best (profiles/r01g_exp_encode_grid.log: 4.7 -> 5.6 TB/s against 4096)
-    const int tbe = g_tune_blocks.load();
-    const uint64_t ecap = tbe > 0 ? (uint64_t)tbe : 0x7fffffffull;
-    if (blocks > ecap) blocks = ecap;
-    if (blocks == 0) blocks = 1;
-    const dim3 grid((unsigned)blocks), block(BB_BLOCK);
+    const dim3 grid = capped_grid((nquad / 256 / eruns + 3) / 4 + 1, BB_GRID_MAX), block(BB_BLOCK);  // RUNS 256-quad runs per wave
     hipStream_t st = (hipStream_t)stream;
     uint8_t *o = (uint8_t *)d_out;
     bb_perm_t perm = {0, 0, 0};
@@ -2179,12 +2182,7 @@ int bb_encode_mark4(const float *d_in, size_t nwords, int ntrack,
     memcpy(a.mag_bit, mag_bit, opw);
     const uint64_t nquad = (uint64_t)nwords * (ntrack / 8);
     // four quads per lane (measured optimum, profiles/r01g_exp_encode_grid.log)
-    uint64_t blocks = (nquad + 4 * BB_BLOCK - 1) / (4 * BB_BLOCK);
-    const int tbm = g_tune_blocks.load();
-    const uint64_t mcap = tbm > 0 ? (uint64_t)tbm : 0x7fffffffull;
-    if (blocks > mcap) blocks = mcap;
-    if (blocks == 0) blocks = 1;
-    const dim3 grid((unsigned)blocks), block(BB_BLOCK);
+    const dim3 grid = capped_grid((nquad + 4 * BB_BLOCK - 1) / (4 * BB_BLOCK), BB_GRID_MAX), block(BB_BLOCK);
     hipStream_t st = (hipStream_t)stream;
     { const int rc_ = ensure_init(); if (rc_) return rc_; }
     const bool direct = g_tune_encode_direct.load() != 0;

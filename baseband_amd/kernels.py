@@ -154,17 +154,8 @@ def vdif_scan(dbuf, nframes, frame_nbytes, header_nbytes, pattern, mask,
     thread_id | flags << 16 (the 16-byte bb_frame_rec).  `set_nframes`:
     frames per frame set in file order -- sets are then formed as the
     reference's VDIFFrameSet.fromfile forms them (include/bbdecode.h)."""
-    p = _lib.VDIFScanParams()
+    p = _vdif_params(frame_nbytes, header_nbytes, pattern, mask, ref_seconds, ref_frame_nr, frame_rate, first_offset)
     p.set_nframes = set_nframes
-    p.first_offset = first_offset
-    p.frame_nbytes = frame_nbytes
-    p.header_nbytes = header_nbytes
-    for i in range(8):
-        p.pattern[i] = int(pattern[i]) if i < len(pattern) else 0
-        p.mask[i] = int(mask[i]) if i < len(mask) else 0
-    p.ref_seconds = ref_seconds
-    p.ref_frame_nr = ref_frame_nr
-    p.frame_rate = frame_rate
     recs = torch.empty((nframes, 4), dtype=torch.int32, device=dbuf.device)
     check(lib.bb_vdif_scan(_ptr(dbuf), dbuf.numel(), C.byref(p), _ptr(recs),
                            nframes, _stream(dbuf)), 'bb_vdif_scan')
@@ -186,6 +177,26 @@ def _vdif_params(frame_nbytes, header_nbytes, pattern, mask, ref_seconds,
     return p
 
 
+def _mark5b_params(ref_seconds, ref_frame_nr, frame_rate, first_offset=0):
+    p = _lib.Mark5BScanParams()
+    p.first_offset, p.ref_seconds = first_offset, ref_seconds
+    p.ref_frame_nr, p.frame_rate = ref_frame_nr, frame_rate
+    return p
+
+
+def _mark4_params(ntrack, ref_year, ref_qms, frame_qms, first_offset=0):
+    p = _lib.Mark4ScanParams()
+    p.first_offset, p.ntrack, p.ref_year = first_offset, ntrack, ref_year
+    p.ref_qms, p.frame_qms = ref_qms, frame_qms
+    return p
+
+
+def _side_handles(verified, scan_stream):
+    """(event, side stream) as the window calls take them: raw handles, null for none."""
+    return (C.c_void_p(verified) if verified else C.c_void_p(0),
+            C.c_void_p(scan_stream.cuda_stream) if scan_stream is not None else C.c_void_p(0))
+
+
 _NSCRATCH = 4       # sets of window scratch taking turns when the scan runs on a side stream
 
 
@@ -204,6 +215,12 @@ class _FrameWindow:
     again the side stream waits for the event recorded behind the decode that
     used it last (16 bytes per frame and 8 per index entry each)."""
     __slots__ = ('recs', 'src', 'fill_value', '_sets', '_turn', '_rotating')
+
+    def set_fill(self, fill_value):
+        """Fill of the windows whose decode takes a `DecodeParams` (`self.dec`)."""
+        fv = complex(fill_value)
+        self.dec.fill_re, self.dec.fill_im = fv.real, fv.imag
+        self.fill_value = fill_value
 
     def _scratch(self, nframes, n, dev, scan_stream=None):
         sets = getattr(self, '_sets', None)
@@ -268,11 +285,6 @@ class VDIFWindow(_FrameWindow):
         self.set_fill(fill_value)
         self.recs = self.src = self._sets = None
 
-    def set_fill(self, fill_value):
-        fv = complex(fill_value)
-        self.dec.fill_re, self.dec.fill_im = fv.real, fv.imag
-        self.fill_value = fill_value
-
     def run(self, dbuf, ref_frame_nr, nframes, thread_slot, nsets, within, out,
             recs_per_index, nstrict, nbad, verified, scan_stream=None):
         """Launch the window on torch's current stream.  `out`: flat float32
@@ -293,9 +305,7 @@ class VDIFWindow(_FrameWindow):
             _ptr(dbuf), dbuf.numel(), C.byref(self.scan), nframes, _ptr(thread_slot), nsets,
             C.byref(self.dec), _ptr(within), nsel, _ptr(self.recs), _ptr(self.src),
             _ptr(tgt.use), tgt.use.numel(), recs_per_index, nstrict, _ptr(nbad),
-            C.c_void_p(verified) if verified else C.c_void_p(0),
-            C.c_void_p(scan_stream.cuda_stream) if scan_stream is not None else C.c_void_p(0),
-            _stream(dbuf)), 'bb_vdif_read_window')
+            *_side_handles(verified, scan_stream), _stream(dbuf)), 'bb_vdif_read_window')
         self._decode_queued(st, scan_stream, dev)
         tgt.done()
 
@@ -306,17 +316,11 @@ class Mark5BWindow(_FrameWindow):
     __slots__ = ('scan', 'dec')
 
     def __init__(self, ref_seconds, frame_rate, bps, chunk, fill_value):
-        p = self.scan = _lib.Mark5BScanParams()
-        p.first_offset, p.ref_seconds, p.frame_rate = 0, ref_seconds, frame_rate
+        self.scan = _mark5b_params(ref_seconds, 0, frame_rate)
         d = self.dec = _lib.DecodeParams()
         d.coder, d.bps, d.chunk, d.nslot, d.payload_nbytes = _lib.CODER_MARK5B, bps, chunk, 1, 10000
         self.recs = self.src = self._sets = None
         self.set_fill(fill_value)
-
-    def set_fill(self, fill_value):
-        fv = complex(fill_value)
-        self.dec.fill_re, self.dec.fill_im = fv.real, fv.imag
-        self.fill_value = fill_value
 
     def run(self, dbuf, ref_frame_nr, nframes, n, within, out, nstrict, nbad, verified, scan_stream=None):
         self.scan.ref_frame_nr = ref_frame_nr
@@ -328,9 +332,8 @@ class Mark5BWindow(_FrameWindow):
         check(lib.bb_mark5b_read_window(
             _ptr(dbuf), dbuf.numel(), C.byref(self.scan), nframes, n, C.byref(self.dec), _ptr(within),
             within.numel() if within is not None else 0, _ptr(self.recs), _ptr(self.src), _ptr(tgt.use),
-            tgt.use.numel(), nstrict, _ptr(nbad), C.c_void_p(verified) if verified else C.c_void_p(0),
-            C.c_void_p(scan_stream.cuda_stream) if scan_stream is not None else C.c_void_p(0),
-            _stream(dbuf)), 'bb_mark5b_read_window')
+            tgt.use.numel(), nstrict, _ptr(nbad), *_side_handles(verified, scan_stream), _stream(dbuf)),
+            'bb_mark5b_read_window')
         self._decode_queued(st, scan_stream, dbuf.device)
         tgt.done()
 
@@ -342,8 +345,7 @@ class Mark4Window(_FrameWindow):
 
     def __init__(self, ntrack, ref_year, ref_qms, frame_qms, nwords, sign_bit, mag_bit, select, fill_words,
                  fill_value):
-        p = self.scan = _lib.Mark4ScanParams()
-        p.first_offset, p.ntrack, p.ref_year, p.frame_qms = 0, ntrack, ref_year, frame_qms
+        self.scan = _mark4_params(ntrack, ref_year, 0, frame_qms)
         self.ref_qms, self.frame_qms = ref_qms, frame_qms
         d = self.dec = _lib.Mark4DecodeParams()
         d.ntrack, d.nwords, d.fill_words = ntrack, nwords, fill_words
@@ -367,9 +369,7 @@ class Mark4Window(_FrameWindow):
         check(lib.bb_mark4_read_window(
             _ptr(dbuf), dbuf.numel(), C.byref(self.scan), nframes, n, C.byref(self.dec), self.nout,
             _ptr(self.recs), _ptr(self.src), _ptr(tgt.use), tgt.use.numel(), nstrict, _ptr(nbad),
-            C.c_void_p(verified) if verified else C.c_void_p(0),
-            C.c_void_p(scan_stream.cuda_stream) if scan_stream is not None else C.c_void_p(0),
-            _stream(dbuf)), 'bb_mark4_read_window')
+            *_side_handles(verified, scan_stream), _stream(dbuf)), 'bb_mark4_read_window')
         self._decode_queued(st, scan_stream, dbuf.device)
         tgt.done()
 
@@ -400,11 +400,7 @@ def vdif_scan_at(dbuf, nbytes, offsets, frame_nbytes, header_nbytes, pattern,
 
 def mark5b_scan(dbuf, nframes, ref_seconds, ref_frame_nr, frame_rate,
                 first_offset=0):
-    p = _lib.Mark5BScanParams()
-    p.first_offset = first_offset
-    p.ref_seconds = ref_seconds
-    p.ref_frame_nr = ref_frame_nr
-    p.frame_rate = frame_rate
+    p = _mark5b_params(ref_seconds, ref_frame_nr, frame_rate, first_offset)
     recs = torch.empty((nframes, 4), dtype=torch.int32, device=dbuf.device)
     check(lib.bb_mark5b_scan(_ptr(dbuf), dbuf.numel(), C.byref(p), _ptr(recs),
                              nframes, _stream(dbuf)), 'bb_mark5b_scan')
@@ -430,9 +426,7 @@ def mark5b_locate(dbuf, nbytes, w1_pattern=0, w1_mask=0):
 
 
 def mark5b_scan_at(dbuf, nbytes, offsets, ref_seconds, ref_frame_nr, frame_rate):
-    p = _lib.Mark5BScanParams()
-    p.first_offset, p.ref_seconds = 0, ref_seconds
-    p.ref_frame_nr, p.frame_rate = ref_frame_nr, frame_rate
+    p = _mark5b_params(ref_seconds, ref_frame_nr, frame_rate)
     n = offsets.numel()
     recs = torch.empty((n, 4), dtype=torch.int32, device=dbuf.device)
     check(lib.bb_mark5b_scan_at(_ptr(dbuf), nbytes, C.byref(p), _ptr(offsets), n,
@@ -459,9 +453,7 @@ def mark4_header_crc(dbuf, nframes, ntrack, first_offset=0, offsets=None):
 
 
 def mark4_scan_at(dbuf, nbytes, offsets, ntrack, ref_year, ref_qms, frame_qms):
-    p = _lib.Mark4ScanParams()
-    p.first_offset, p.ntrack, p.ref_year = 0, ntrack, ref_year
-    p.ref_qms, p.frame_qms = ref_qms, frame_qms
+    p = _mark4_params(ntrack, ref_year, ref_qms, frame_qms)
     n = offsets.numel()
     recs = torch.empty((n, 4), dtype=torch.int32, device=dbuf.device)
     check(lib.bb_mark4_scan_at(_ptr(dbuf), nbytes, C.byref(p), _ptr(offsets), n,
@@ -602,12 +594,7 @@ def select_supported(bps, chunk, nslot, nwithin, payload_nbytes=None):
 
 def mark4_scan(dbuf, nframes, ntrack, ref_year, ref_qms, frame_qms,
                first_offset=0):
-    p = _lib.Mark4ScanParams()
-    p.first_offset = first_offset
-    p.ntrack = ntrack
-    p.ref_year = ref_year
-    p.ref_qms = ref_qms
-    p.frame_qms = frame_qms
+    p = _mark4_params(ntrack, ref_year, ref_qms, frame_qms, first_offset)
     recs = torch.empty((nframes, 4), dtype=torch.int32, device=dbuf.device)
     check(lib.bb_mark4_scan(_ptr(dbuf), dbuf.numel(), C.byref(p), _ptr(recs),
                             nframes, _stream(dbuf)), 'bb_mark4_scan')

@@ -346,6 +346,12 @@ int bb_build_index(const bb_frame_rec *d_recs, size_t nrecs,
  * fill, exactly like -1; nothing outside the buffer is read.  The reference
  * never returns garbage for bytes a file does not hold either (short read ->
  * EOFError, base/payload.py:135-136).
+ *
+ * An empty request (nframes == 0) launches nothing and touches no buffer.  Its
+ * answer depends on the output type: for float32 it is BB_OK as soon as
+ * (coder, bps) is supported -- the rest of the parameter block is not looked at;
+ * for BB_OUT_F16 / BB_OUT_BF16 it is BB_OK only when the whole parameter block
+ * passes (what bb_decode_out_check answers), else that check's code.
  */
 typedef struct bb_decode_params {
     int32_t  coder;            /* enum bb_coder */
