@@ -119,6 +119,13 @@ class DecodeParams(C.Structure):
                 ('fill_im', C.c_float), ('out_type', C.c_int32)]
 
 
+class StatesParams(C.Structure):
+    _fields_ = [('bps', C.c_int32), ('chunk', C.c_int32), ('nslot', C.c_int32),
+                ('reserved', C.c_int32), ('payload_nbytes', C.c_uint64),
+                ('src0', C.c_int64), ('src_stride', C.c_int64),
+                ('row_lo', C.c_uint64), ('row_hi', C.c_uint64)]
+
+
 class Mark4ScanParams(C.Structure):
     _fields_ = [('first_offset', C.c_uint64), ('ntrack', C.c_int32),
                 ('ref_year', C.c_int32), ('ref_qms', C.c_int64),
@@ -202,6 +209,8 @@ SIGNATURES = [
     ('bb_decode_frames_select', C.c_int, [_vp, _sz, _vp, _sz, C.POINTER(DecodeParams), _vp, C.c_int, _vp, _sz, _vp]),
     ('bb_decode_frames_select_check', C.c_int, [C.POINTER(DecodeParams), C.c_int]),
     ('bb_copy_frames', C.c_int, [_vp, _sz, _sz, C.c_uint64, C.c_int64, C.c_int64, _vp, _sz, _vp]),
+    ('bb_count_states', C.c_int, [_vp, _sz, _vp, _sz, C.POINTER(StatesParams), _vp, _sz, _vp]),
+    ('bb_count_states_check', C.c_int, [C.POINTER(StatesParams)]),
     ('bb_fetch_counter', C.c_int, [_vp, _vp, _vp, _vp]),
     ('bb_mark5b_read_window', C.c_int, [_vp, _sz, C.POINTER(Mark5BScanParams), _sz, _sz, C.POINTER(DecodeParams),
                                         _vp, C.c_int, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
@@ -269,6 +278,15 @@ def get_levels(coder, bps):
     check(lib.bb_get_levels(coder, bps, out.ctypes.data_as(C.POINTER(C.c_float)), n),
           'bb_get_levels')
     return out
+
+
+def count_states_check(bps, chunk=1, nslot=1, payload_nbytes=4, row_lo=0, row_hi=0, reserved=0):
+    """What `bb_count_states` would answer to these parameters, as far as they decide it
+    (bb_count_states_check: no buffers, no device): BB_OK, BB_EINVAL or BB_ENOTSUP."""
+    p = StatesParams()
+    p.bps, p.chunk, p.nslot, p.reserved = bps, chunk, nslot, reserved
+    p.payload_nbytes, p.row_lo, p.row_hi = payload_nbytes, row_lo, row_hi
+    return lib.bb_count_states_check(C.byref(p))
 
 
 def out_type_of(dtype):

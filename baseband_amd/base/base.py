@@ -20,6 +20,7 @@ import warnings
 import numpy as np
 import torch
 
+from .. import _lib
 from .. import kernels
 from ..placement import empty_output
 from .. import placement as _placement
@@ -990,6 +991,99 @@ class GPUStreamReaderBase:
         else:
             _to_host_array(data, out)
         return out
+
+    # -- sampler statistics (kernels.count_states; readers whose frames are fixed-stride
+    #    payloads of LSB-first codes define `_states_geometry` and `_states_index`)
+    def _states_geometry(self):
+        """(coder, bps, chunk, nslot, payload_nbytes) of the packed samples, or None."""
+        return None
+
+    def _states_index(self, dbuf, first, nsets):
+        """Payload offsets into `dbuf`, which starts at frame set `first`, for `nsets`
+        frame sets (-1: missing or invalid): header scan and index, nothing else."""
+        raise NotImplementedError
+
+    def _states_shape(self, counts):
+        return counts
+
+    @property
+    def state_levels(self):
+        """float32 NumPy array of the ``2**bps`` levels of this stream's coder, by raw
+        code: with ``c = fh.state_counts()``, ``(c * levels**2).sum(-1) / c.sum(-1)`` is
+        the mean power."""
+        geom = self._states_geometry()
+        if geom is None:
+            raise NotImplementedError("{} has no sampler statistics".format(type(self).__name__))
+        return _lib.get_levels(geom[0], geom[1])
+
+    def state_counts(self, count=None):
+        """How often each raw sample code occurs among the samples ``read(count)``
+        would return from the current offset -> int64 device tensor whose last axis
+        counts codes ``0 .. 2**bps - 1`` (levels: `state_levels`).  Counted from the
+        packed bytes (bb_count_states): one pass over the file's bytes, nothing is
+        decoded and the offset does not move.  Samples of frames that ``read()`` would
+        fill (missing or invalid ones) are left out; bad frames do not raise.  Threads
+        follow the reader's selection; a channel `subset` is NOT applied: counting
+        every channel costs nothing more."""
+        if self.closed:
+            raise ValueError("I/O operation on closed stream.")
+        geom = self._states_geometry()
+        if geom is None:
+            raise NotImplementedError("{} has no sampler statistics".format(type(self).__name__))
+        _, bps, chunk, nslot, payload = geom
+        if not kernels.count_states_supported(bps, chunk, nslot, payload):
+            raise NotImplementedError(
+                "state_counts: a complete sample of {} codes x {} bits is not one the counting kernel "
+                "takes (a power of two of codes, chunk * bps <= {})".format(chunk, bps, kernels.STATES_MAX_ROW_BITS))
+        samples_left = self.shape[0] - self.offset
+        if count is None or count < 0:
+            count = max(0, samples_left)
+        if count > samples_left:
+            raise EOFError("cannot read from beyond end of input.")
+        kernels.require_gpu()
+        counts = torch.zeros((nslot, chunk, 1 << bps), dtype=torch.int64, device='cuda')
+        if count == 0:
+            return self._states_shape(counts)
+        spf = self.samples_per_frame
+        start, stop = self.offset, self.offset + count
+        first, last = start // spf, -(-stop // spf)
+        set_nbytes = self._set_nbytes
+
+        def add(dbuf, src, s, e):
+            kernels.count_states(dbuf, e - s, payload, bps, chunk, nslot, src=src,
+                                 row_lo=max(start, s * spf) - s * spf, row_hi=min(stop, e * spf) - s * spf,
+                                 counts=counts)
+
+        located = getattr(self, '_resident', None)
+        resident = self._resident_bytes()
+        if located is not None:
+            # a re-located index (bytes went missing): offsets into the whole file in HBM
+            dev, src = located
+            add(dev, src[first * nslot:last * nslot].contiguous(), first, last)
+        elif resident is not None:
+            lo = min(self._file_offset0 + first * set_nbytes, resident.numel())
+            hi = max(lo, min(self._file_offset0 + last * set_nbytes, resident.numel()))
+            win = self._device_window(resident, lo, hi)
+            add(win, self._states_index(win, first, last - first), first, last)
+        else:
+            image = self._image()
+            per_win = min(last - first, max(1, self.window_bytes // set_nbytes))
+            pipe = WindowPipeline(image, per_win * set_nbytes)
+            ranges, spans = [], []
+            for s in range(first, last, per_win):
+                e = min(last, s + per_win)
+                lo = min(self._file_offset0 + s * set_nbytes, len(image))
+                ranges.append((lo, max(lo, min(self._file_offset0 + e * set_nbytes, len(image)))))
+                spans.append((s, e))
+
+            def process(dbuf, i):
+                s, e = spans[i]
+                win = self._device_window(dbuf, 0, dbuf.numel())
+                add(win, self._states_index(win, s, e - s), s, e)
+
+            pipe.run(ranges, process)
+            pipe.release()
+        return self._states_shape(counts)
 
     # ``host_results = True``: ``read()`` without `out` returns NEW NumPy arrays, as the
     # reference does (what the ``baseband.io`` plugin modules switch on): arrays on pinned

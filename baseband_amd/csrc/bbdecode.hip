@@ -12,6 +12,7 @@
 #include "k_half.h"
 #include "bb_half_host.h"
 #include "k_copy.h"
+#include "k_states.h"
 #include "k_tfpick.h"
 #if BB_EXP
 #include "k_burst.h"
@@ -23,6 +24,7 @@
 #include "k_xpose.h"
 #include "k_encode.h"
 
+#include <algorithm>
 #include <atomic>
 #include <mutex>
 #include <stdio.h>
@@ -1563,6 +1565,77 @@ int bb_copy_frames(const void *d_buf, size_t buf_nbytes, size_t nframes, uint64_
     });
     (void)ntl;
     BB_NOTE("k_copy_frames<%s,%s,%d,%s> grid %u", nt ? "nt" : "plain", v16 ? "16B" : "4B", nl, ntl ? "ntload" : "load", grid.x);
+    BB_HIP(hipGetLastError());
+    return BB_OK;
+}
+
+// ---- sampler statistics (k_states.h).  EXTENSION: no reference counterpart. ----
+static int states_params_check(const bb_states_params *p)
+{
+    if (!p) return BB_EINVAL;
+    if (log2_bps(p->bps) < 0) return BB_ENOTSUP;
+    if (p->reserved != 0 || p->nslot < 1 || p->chunk < 1) return BB_EINVAL;
+    if (p->chunk & (p->chunk - 1)) return BB_ENOTSUP;
+    if ((int64_t)p->chunk * p->bps > 8 * (int64_t)BB_STATES_MAX_PHASES) return BB_ENOTSUP;   // the byte phases kept on chip
+    if (p->payload_nbytes == 0 || (p->payload_nbytes & 3) || p->payload_nbytes > (1ull << 56)) return BB_EINVAL;
+    if ((p->payload_nbytes * 8 / (uint64_t)p->bps) % (uint64_t)p->chunk) return BB_EINVAL;   // whole rows
+    if (p->row_lo > p->row_hi) return BB_EINVAL;
+    return BB_OK;
+}
+
+int bb_count_states_check(const bb_states_params *p) { return states_params_check(p); }
+
+#define BB_STATES_GRID 2048ull                       // workgroups: what 256 CUs hold at once; each flushes once
+#define BB_STATES_WAVE_ITEMS (1ull << 19)            // work items a wave may see: 2^31 bytes, its 32-bit counters cannot wrap
+
+int bb_count_states(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size_t nframes,
+                    const bb_states_params *p, unsigned long long *d_counts, size_t ncounts, void *stream)
+{
+    int rc = states_params_check(p);
+    if (rc) return rc;
+    if (!d_counts || ((uintptr_t)d_counts & 7)) return BB_EINVAL;
+    const uint64_t nbins = ((uint64_t)p->nslot * (uint64_t)p->chunk) << p->bps;
+    if (ncounts < nbins) return BB_ERANGE;
+    const uint64_t R = p->payload_nbytes * 8 / (uint64_t)p->bps / (uint64_t)p->chunk;
+    if (nframes && R > (~0ull) / (uint64_t)nframes) return BB_ERANGE;
+    if (p->row_hi > (uint64_t)nframes * R) return BB_ERANGE;
+    if (nframes == 0 || p->row_lo == p->row_hi) return BB_OK;
+    if (!d_buf || ((uintptr_t)d_buf & 3)) return BB_EINVAL;
+    const uint64_t nfs = (uint64_t)nframes * (uint64_t)p->nslot;
+    if (!d_src) {
+        rc = fixed_stride_check(p->src0, p->src_stride, 4, nfs, p->payload_nbytes, buf_nbytes);
+        if (rc) return rc;
+    }
+    bb_states_args a;
+    a.buf = (const uint8_t *)d_buf;
+    a.src = d_src;
+    a.counts = d_counts;
+    a.src_lim = src_limit(buf_nbytes, p->payload_nbytes);
+    a.src0 = p->src0; a.src_stride = p->src_stride;
+    a.payload = p->payload_nbytes;
+    a.R = R;
+    a.row_lo = p->row_lo; a.row_hi = p->row_hi;
+    a.f_lo = p->row_lo / R;
+    const uint64_t nfr = (p->row_hi + R - 1) / R - a.f_lo;          // frames that hold a counted row
+    const uint64_t nseg = (p->payload_nbytes + BB_STATES_SEG - 1) / BB_STATES_SEG;
+    if (nseg > 0xffffffffull || nfr > (~0ull) / nseg) return BB_ERANGE;
+    a.nseg = (uint32_t)nseg;
+    a.seg_bytes = (uint32_t)((((p->payload_nbytes + nseg - 1) / nseg) + 15) & ~15ull);   // even pieces of at most BB_STATES_SEG
+    a.nwork = nfr * nseg;
+    a.nslot = (uint32_t)p->nslot; a.chunk = (uint32_t)p->chunk;
+    a.bps = (uint32_t)p->bps; a.lbps = (uint32_t)log2_bps(p->bps);
+    const uint32_t cb = a.chunk * a.bps;
+    a.lphase = cb > 8 ? ceil_log2(cb / 8) : 0;
+    // workgroups per slot: one wave per work item up to what the device holds at once, and
+    // enough of them that no wave walks more than BB_STATES_WAVE_ITEMS
+    const int tb = g_tune_blocks.load();
+    const uint64_t cap = std::max<uint64_t>(1, (tb > 0 ? (uint64_t)tb : BB_STATES_GRID) / a.nslot);
+    uint64_t g = std::min<uint64_t>((a.nwork + BB_WAVES_PER_BLOCK - 1) / BB_WAVES_PER_BLOCK, cap);
+    const uint64_t need = (a.nwork + BB_WAVES_PER_BLOCK * BB_STATES_WAVE_ITEMS - 1) / (BB_WAVES_PER_BLOCK * BB_STATES_WAVE_ITEMS);
+    if (g < need) g = need;
+    if (g * a.nslot > BB_GRID_MAX) return BB_ERANGE;
+    const size_t lds = ((size_t)BB_WAVES_PER_BLOCK << (8 + a.lphase)) * 4 + (cb < 8 ? 64 : 0);
+    hipLaunchKernelGGL(k_count_states, dim3((unsigned)(g * a.nslot)), dim3(BB_BLOCK), lds, (hipStream_t)stream, a);
     BB_HIP(hipGetLastError());
     return BB_OK;
 }

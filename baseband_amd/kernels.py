@@ -399,8 +399,9 @@ def vdif_scan_at(dbuf, nbytes, offsets, frame_nbytes, header_nbytes, pattern,
 
 
 def mark5b_scan(dbuf, nframes, ref_seconds, ref_frame_nr, frame_rate,
-                first_offset=0):
+                first_offset=0, by_position=False):
     p = _mark5b_params(ref_seconds, ref_frame_nr, frame_rate, first_offset)
+    p.by_position = int(bool(by_position))
     recs = torch.empty((nframes, 4), dtype=torch.int32, device=dbuf.device)
     check(lib.bb_mark5b_scan(_ptr(dbuf), dbuf.numel(), C.byref(p), _ptr(recs),
                              nframes, _stream(dbuf)), 'bb_mark5b_scan')
@@ -552,6 +553,43 @@ def copy_frames(dbuf, nframes, nbytes_per_frame, src0=0, src_stride=0, out=None)
     check(lib.bb_copy_frames(_ptr(dbuf), dbuf.numel(), nframes, nbytes_per_frame, src0, src_stride,
                              _ptr(tgt.use), tgt.use.numel() * 4, _stream(dbuf)), 'bb_copy_frames')
     return tgt.done()
+
+
+STATES_MAX_ROW_BITS = 128      # chunk * bps the counting kernel takes (16 byte phases on chip)
+
+
+def count_states_supported(bps, chunk=1, nslot=1, payload_nbytes=None):
+    """Would `count_states` take this geometry?  (bb_count_states_check; no device needed.)"""
+    if payload_nbytes is None:
+        payload_nbytes = max(4, chunk * bps // 8) if bps in (1, 2, 4, 8) else 4
+    return _lib.count_states_check(bps, chunk, nslot, payload_nbytes) == _lib.BB_OK
+
+
+def count_states(dbuf, nframes, payload_nbytes, bps, chunk=1, nslot=1, src=None, src0=0,
+                 src_stride=0, row_lo=0, row_hi=None, counts=None):
+    """Sampler statistics from packed bytes (bb_count_states; EXTENSION, no reference
+    counterpart): how often each raw code occurs per (thread slot, position in a row) among
+    rows [row_lo, row_hi) of `nframes` frame(set)s -> int64 device tensor of shape
+    ``(nslot, chunk, 1 << bps)``.  Frame-slots are taken through the index `src` (-1 or an
+    offset outside the buffer: not counted) or at ``src0 + k * src_stride``.  With `counts`
+    (such a tensor, contiguous) the call ADDS to it.  Codes are raw: the level of code c is
+    ``_lib.get_levels(coder, bps)[c]``.  Nothing is decoded and nothing synchronises."""
+    p = _lib.StatesParams()
+    p.bps, p.chunk, p.nslot, p.reserved = bps, chunk, nslot, 0
+    p.payload_nbytes = payload_nbytes
+    p.src0, p.src_stride = src0, src_stride
+    if row_hi is None:
+        row_hi = nframes * (payload_nbytes * 8 // bps // chunk) if bps in (1, 2, 4, 8) and chunk > 0 else 0
+    p.row_lo, p.row_hi = row_lo, row_hi
+    if counts is None:
+        rc = lib.bb_count_states_check(C.byref(p))      # (before a shape is made of the parameters)
+        check(rc, 'bb_count_states')
+        counts = torch.zeros((nslot, chunk, 1 << bps), dtype=torch.int64, device=dbuf.device)
+    elif counts.dtype != torch.int64 or not counts.is_contiguous():
+        raise TypeError("counts must be a contiguous int64 tensor")
+    check(lib.bb_count_states(_ptr(dbuf), dbuf.numel(), _ptr(src), nframes, C.byref(p),
+                              _ptr(counts), counts.numel(), _stream(dbuf)), 'bb_count_states')
+    return counts
 
 
 TOUCH_MIN_BYTES = 16 << 20

@@ -220,6 +220,22 @@ class Mark5BStreamReader(GPUStreamReaderBase):
         return flat.reshape(((last - first) * self.samples_per_frame,)
                             + tuple(self._decode_shape))
 
+    # -- sampler statistics (base.state_counts)
+    def _states_geometry(self):
+        return (_lib.CODER_MARK5B, self.bps, self._unsliced_shape[0], 1, 10000)
+
+    def _states_index(self, dbuf, first, nsets):
+        nframes = min(nsets, dbuf.numel() // FRAME_NBYTES)
+        if nframes == 0:
+            return torch.full((nsets,), -1, dtype=torch.int64, device=dbuf.device)
+        recs = kernels.mark5b_scan(dbuf, nframes, self._ref_seconds, self.header0['frame_nr'] + first,
+                                   self._frame_rate, by_position=not self.verify)
+        return kernels.build_index(recs, nsets, 1, None)
+
+    def _states_shape(self, counts):
+        """(nchan, 2**bps)."""
+        return counts[0]
+
     _window = None          # kernels.Mark5BWindow: argument blocks of the one-call window
 
     def _side_state_key(self):

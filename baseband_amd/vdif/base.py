@@ -663,6 +663,32 @@ class VDIFStreamReader(GPUStreamReaderBase):
         if self.verify:
             self._note_checked(nframes, missing=nsets * nthread_file - nframes)
 
+    # -- sampler statistics (base.state_counts)
+    def _states_geometry(self):
+        h0 = self.header0
+        return (self._coder, self.bps, h0.nchan * (2 if self.complex_data else 1), len(self._thread_ids),
+                h0.payload_nbytes)
+
+    def _states_index(self, dbuf, first, nsets):
+        """The un-fused scan and index of `build_index` for the frame sets `dbuf` starts with."""
+        h0 = self.header0
+        nslot = len(self._thread_ids)
+        nthread_file = len(self._file_threads)
+        nframes = min(nsets * nthread_file, dbuf.numel() // self._frame_nbytes)
+        if nframes == 0:
+            return torch.full((nsets * nslot,), -1, dtype=torch.int64, device=dbuf.device)
+        if self._thread_slot is None:
+            self._thread_slot = kernels.thread_slot_map(self._thread_ids, dbuf.device)
+        recs = kernels.vdif_scan(dbuf, nframes, self._frame_nbytes, h0.nbytes, self._pattern,
+                                 self._mask if self.verify else [0] * len(self._mask), h0['seconds'],
+                                 h0['frame_nr'] + first, self._frame_rate, set_nframes=nthread_file)
+        return kernels.build_index(recs, nsets, nslot, self._thread_slot)
+
+    def _states_shape(self, counts):
+        """(nthread, nchan, 2**bps); complex data: (nthread, nchan, 2, 2**bps), (re, im)."""
+        nchan = self.header0.nchan
+        return counts.reshape((counts.shape[0], nchan) + ((2,) if self.complex_data else ()) + counts.shape[-1:])
+
     # -- frame index as a first-class object (multi-GPU sharding, parallel.py)
     def build_index(self, first=0, last=None):
         """Dense device index of frame sets [first, last): int64 payload

@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define BB_ABI_VERSION 7   /* 7, additive: bb_decode_params.reserved became out_type (zero = float32, the old behaviour; same layout), bb_mark4_decode_params.reserved likewise (float32 only), bb_decode_out_check, bb_get_levels_as */   /* 7 (round 6): bb_touch; the *_read_window calls read small windows through first */   /* 6 (round 6): bb_mark5b_locate_stream */   /* 5 (round 6): bb_arena_stats grew (first_probe_gbps .. second_chance_wins) */   /* 4 (round 5): bb_arena_prepare, bb_arena_owns, bb_arena_stats grew (va_ranges .. prepare_wait_ms); the `reserved` words of the scan parameter blocks got meanings whose zero is the old behaviour (bb_vdif_scan_params.set_nframes, bb_mark5b_/bb_mark4_scan_params.by_position): same layout  */   /* 3 (round 4): bb_copy_frames; bb_arena_stats grew va_reserved / va_used; bb_tune knobs are thread-local */   /* 2: bb_tiled_params grew (npol_stored, pol_first, d_chan_map) */
+#define BB_ABI_VERSION 7   /* 7, additive: bb_count_states, bb_count_states_check, bb_states_params (sampler statistics; nothing else changed) */   /* 7, additive: bb_decode_params.reserved became out_type (zero = float32, the old behaviour; same layout), bb_mark4_decode_params.reserved likewise (float32 only), bb_decode_out_check, bb_get_levels_as */   /* 7 (round 6): bb_touch; the *_read_window calls read small windows through first */   /* 6 (round 6): bb_mark5b_locate_stream */   /* 5 (round 6): bb_arena_stats grew (first_probe_gbps .. second_chance_wins) */   /* 4 (round 5): bb_arena_prepare, bb_arena_owns, bb_arena_stats grew (va_ranges .. prepare_wait_ms); the `reserved` words of the scan parameter blocks got meanings whose zero is the old behaviour (bb_vdif_scan_params.set_nframes, bb_mark5b_/bb_mark4_scan_params.by_position): same layout  */   /* 3 (round 4): bb_copy_frames; bb_arena_stats grew va_reserved / va_used; bb_tune knobs are thread-local */   /* 2: bb_tiled_params grew (npol_stored, pol_first, d_chan_map) */
 
 /* error codes (negative errno values) */
 #define BB_OK        0
@@ -629,6 +629,56 @@ int bb_mark4_read_window(const void *d_buf, size_t nbytes,
 int bb_copy_frames(const void *d_buf, size_t buf_nbytes, size_t nframes,
                    uint64_t nbytes_per_frame, int64_t src0, int64_t src_stride,
                    void *d_out, size_t out_nbytes, void *stream);
+
+/* ---- sampler statistics (extension) -------------------------------------- */
+
+/*
+ * How often every raw code occurs, per thread slot and position in a row,
+ * counted from the packed bytes without decoding them.  EXTENSION -- the
+ * reference has no counterpart (its users decode and compare, or run m5bstate /
+ * vdifbstate on the file).  A "code" is a field of the payload taken LSB first,
+ * the order of vdif/payload.py:25-103 and mark5b/payload.py:27-94: code e of
+ * the payload of frame f, slot s is field e % (8/bps) of byte e / (8/bps); with
+ * raw value c it ADDS one to
+ *     d_counts[((s * chunk + e % chunk) << bps) + c]
+ * when its global row f * R + e / chunk lies in [row_lo, row_hi) and the
+ * frame-slot's source passes the bounds rule of bb_decode_frames: a source of
+ * -1, any negative one, or one whose payload does not lie wholly inside the
+ * buffer counts nothing, and nothing outside the buffer is read.  Counts are of
+ * raw codes, whatever the coder: the level of code c is
+ * bb_get_levels(coder, bps)[c].  The call adds to d_counts (the caller zeroes
+ * it: windows and files accumulate); integer adds commute, so the result is the
+ * same bit for bit from run to run.
+ *
+ * Pointers and payloads as for bb_decode_frames: payloads at any byte address
+ * through an index, a fixed-stride request (d_src == NULL) with src0 and
+ * src_stride multiples of 4 and its last payload inside the buffer (else
+ * BB_ERANGE); d_counts 8-byte aligned; ncounts >= (nslot * chunk) << bps and
+ * row_hi <= nframes * R, else BB_ERANGE.  Stream-ordered, never allocates,
+ * never synchronises; nframes == 0 or row_lo == row_hi launches nothing.
+ *
+ * bb_count_states_check answers what the parameters alone decide (no buffers,
+ * no device): BB_EINVAL (a NULL block, sizes, reserved != 0, a payload that is
+ * not a multiple of 4 or not whole rows, row_lo > row_hi), BB_ENOTSUP (bps not
+ * in {1, 2, 4, 8}, a chunk that is not a power of two, or chunk * bps > 128:
+ * the kernel keeps the at most 16 byte phases of a row on chip).
+ */
+typedef struct bb_states_params {
+    int32_t  bps;             /* 1, 2, 4, 8 */
+    int32_t  chunk;           /* codes per (sample, slot): nchan * (2 if complex); a power of two */
+    int32_t  nslot;           /* thread slots, as in bb_decode_params */
+    int32_t  reserved;        /* 0 */
+    uint64_t payload_nbytes;  /* per frame and slot; a multiple of 4; whole rows */
+    int64_t  src0, src_stride;/* used when d_src == NULL, as in bb_decode_frames */
+    uint64_t row_lo, row_hi;  /* rows (complete samples) [row_lo, row_hi) of the request's
+                                 nframes * R rows are counted, R = payload_nbytes*8/bps/chunk */
+} bb_states_params;
+
+int bb_count_states(const void *d_buf, size_t buf_nbytes,
+                    const int64_t *d_src, size_t nframes,
+                    const bb_states_params *params,
+                    unsigned long long *d_counts, size_t ncounts, void *stream);
+int bb_count_states_check(const bb_states_params *params);
 
 /* ---- byte-aligned formats with an axis permutation --------------------- */
 
