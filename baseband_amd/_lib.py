@@ -211,6 +211,9 @@ SIGNATURES = [
     ('bb_copy_frames', C.c_int, [_vp, _sz, _sz, C.c_uint64, C.c_int64, C.c_int64, _vp, _sz, _vp]),
     ('bb_count_states', C.c_int, [_vp, _sz, _vp, _sz, C.POINTER(StatesParams), _vp, _sz, _vp]),
     ('bb_count_states_check', C.c_int, [C.POINTER(StatesParams)]),
+    ('bb_count_states_bins', C.c_int, [_vp, _sz, _vp, _sz, C.POINTER(StatesParams), C.c_uint64, C.c_uint64,
+                                       C.c_uint64, _vp, _sz, _vp]),
+    ('bb_count_states_bins_check', C.c_int, [C.POINTER(StatesParams), C.c_uint64]),
     ('bb_fetch_counter', C.c_int, [_vp, _vp, _vp, _vp]),
     ('bb_mark5b_read_window', C.c_int, [_vp, _sz, C.POINTER(Mark5BScanParams), _sz, _sz, C.POINTER(DecodeParams),
                                         _vp, C.c_int, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
@@ -287,6 +290,15 @@ def count_states_check(bps, chunk=1, nslot=1, payload_nbytes=4, row_lo=0, row_hi
     p.bps, p.chunk, p.nslot, p.reserved = bps, chunk, nslot, reserved
     p.payload_nbytes, p.row_lo, p.row_hi = payload_nbytes, row_lo, row_hi
     return lib.bb_count_states_check(C.byref(p))
+
+
+def count_states_bins_check(bps, chunk=1, bin_rows=8, nslot=1, payload_nbytes=4, row_lo=0, row_hi=0, reserved=0):
+    """What `bb_count_states_bins` would answer to these parameters, as far as they decide
+    it (bb_count_states_bins_check: no buffers, no device): BB_OK, BB_EINVAL or BB_ENOTSUP."""
+    p = StatesParams()
+    p.bps, p.chunk, p.nslot, p.reserved = bps, chunk, nslot, reserved
+    p.payload_nbytes, p.row_lo, p.row_hi = payload_nbytes, row_lo, row_hi
+    return lib.bb_count_states_bins_check(C.byref(p), bin_rows)
 
 
 def out_type_of(dtype):

@@ -1085,6 +1085,116 @@ class GPUStreamReaderBase:
             pipe.release()
         return self._states_shape(counts)
 
+    def state_series(self, bin_samples, count=None):
+        """`state_counts` as a time series: int32 device tensor of shape ``(nbins,) +
+        state_counts().shape`` with ``nbins = ceil(count / bin_samples)``; bin ``b`` counts
+        the samples ``[offset + b * bin_samples, offset + (b + 1) * bin_samples)`` of what
+        ``read(count)`` would return (the last bin may be short).  Counted from the packed
+        bytes (bb_count_states_bins): one pass, nothing is decoded, the offset does not
+        move.  Samples of missing or invalid frames are left out, so a bin's sum over the
+        code axis is its number of valid samples, and ``state_series(n, count).sum(0)``
+        equals ``state_counts(count)``.  Bins are whole bytes of a thread's stream:
+        `bin_samples`, the offset and `count` must be multiples of ``8 / (codes per sample
+        * bps)`` samples where that is more than one."""
+        if self.closed:
+            raise ValueError("I/O operation on closed stream.")
+        geom = self._states_geometry()
+        if geom is None:
+            raise NotImplementedError("{} has no sampler statistics".format(type(self).__name__))
+        _, bps, chunk, nslot, payload = geom
+        bin_samples = operator.index(bin_samples)
+        if bin_samples < 1:
+            raise ValueError("state_series: bin_samples must be at least 1")
+        if bin_samples > 0x7fffffff:
+            raise ValueError("state_series: bin_samples must be below 2**31")
+        if not kernels.count_states_supported(bps, chunk, nslot, payload) or \
+                chunk << bps > kernels.STATES_BINS_MAX_COUNTERS:
+            raise NotImplementedError(
+                "state_series: a complete sample of {} codes x {} bits is not one the binned counting kernel "
+                "takes (a power of two of codes, chunk * bps <= {}, chunk << bps <= {})".format(
+                    chunk, bps, kernels.STATES_MAX_ROW_BITS, kernels.STATES_BINS_MAX_COUNTERS))
+        samples_left = self.shape[0] - self.offset
+        if count is None or count < 0:
+            count = max(0, samples_left)
+        if count > samples_left:
+            raise EOFError("cannot read from beyond end of input.")
+        whole = max(1, 8 // (chunk * bps))              # samples in a byte of a thread's stream
+        if bin_samples % whole:
+            raise ValueError("state_series: bins are whole bytes: bin_samples must be a multiple of {} "
+                             "samples".format(whole))
+        if self.offset % whole:
+            raise ValueError("state_series: bins are whole bytes: seek to a multiple of {} samples".format(whole))
+        if count % whole:
+            raise ValueError("state_series: bins are whole bytes: count must be a multiple of {} "
+                             "samples".format(whole))
+        if not kernels.count_states_bins_supported(bps, chunk, bin_samples, nslot, payload):
+            raise NotImplementedError("state_series: the binned counting kernel does not take bins of {} samples "
+                                      "of {} codes x {} bits".format(bin_samples, chunk, bps))
+        kernels.require_gpu()
+        nbins = -(-count // bin_samples)
+        counts = torch.zeros((nslot, nbins, chunk, 1 << bps), dtype=torch.int32, device='cuda')
+        shape = tuple(self._states_shape(torch.empty((nslot, chunk, 1 << bps), device='meta')).shape)
+
+        def series():
+            return counts.permute(1, 0, 2, 3).reshape((nbins,) + shape)
+
+        if count == 0:
+            return series()
+        spf = self.samples_per_frame
+        start, stop = self.offset, self.offset + count
+        first, last = start // spf, -(-stop // spf)
+        set_nbytes = self._set_nbytes
+
+        def add(dbuf, src, s, e):
+            lo = max(start, s * spf)
+            kernels.count_states_bins(dbuf, e - s, payload, bps, chunk, nslot, bin_samples, nbins, src=src,
+                                      row_lo=lo - s * spf, row_hi=min(stop, e * spf) - s * spf,
+                                      first_row=lo - start, counts=counts)
+
+        located = getattr(self, '_resident', None)
+        resident = self._resident_bytes()
+        if located is not None:
+            # a re-located index (bytes went missing): offsets into the whole file in HBM
+            dev, src = located
+            add(dev, src[first * nslot:last * nslot].contiguous(), first, last)
+        elif resident is not None:
+            lo = min(self._file_offset0 + first * set_nbytes, resident.numel())
+            hi = max(lo, min(self._file_offset0 + last * set_nbytes, resident.numel()))
+            win = self._device_window(resident, lo, hi)
+            add(win, self._states_index(win, first, last - first), first, last)
+        else:
+            image = self._image()
+            per_win = min(last - first, max(1, self.window_bytes // set_nbytes))
+            pipe = WindowPipeline(image, per_win * set_nbytes)
+            ranges, spans = [], []
+            for s in range(first, last, per_win):
+                e = min(last, s + per_win)
+                lo = min(self._file_offset0 + s * set_nbytes, len(image))
+                ranges.append((lo, max(lo, min(self._file_offset0 + e * set_nbytes, len(image)))))
+                spans.append((s, e))
+
+            def process(dbuf, i):
+                s, e = spans[i]
+                win = self._device_window(dbuf, 0, dbuf.numel())
+                add(win, self._states_index(win, s, e - s), s, e)
+
+            pipe.run(ranges, process)
+            pipe.release()
+        return series()
+
+    def power_series(self, bin_samples, count=None):
+        """Mean ``|x|**2`` per valid sample and time bin, from `state_series`: float64
+        device tensor of shape ``(nbins, nthread, nchan)`` (Mark 5B: ``(nbins, nchan)``),
+        NaN where a bin holds no valid sample.  Exact up to float64 rounding: the power of
+        a bin is ``sum(counts * levels**2)``; nothing is decoded."""
+        counts = self.state_series(bin_samples, count)
+        levels = torch.from_numpy(self.state_levels).to(counts.device).double()
+        power = (counts.double() * levels ** 2).sum(-1)
+        valid = counts.sum(-1, dtype=torch.int64)
+        if self.complex_data:                           # (re, im) axis: a sample has both
+            power, valid = power.sum(-1), valid[..., 0]
+        return power / valid.double()
+
     # ``host_results = True``: ``read()`` without `out` returns NEW NumPy arrays, as the
     # reference does (what the ``baseband.io`` plugin modules switch on): arrays on pinned
     # memory filled by the DMA engine (`staging.download_new`), and -- in loops of small

@@ -13,6 +13,7 @@
 #include "bb_half_host.h"
 #include "k_copy.h"
 #include "k_states.h"
+#include "k_state_bins.h"
 #include "k_tfpick.h"
 #if BB_EXP
 #include "k_burst.h"
@@ -1636,6 +1637,86 @@ int bb_count_states(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, 
     if (g * a.nslot > BB_GRID_MAX) return BB_ERANGE;
     const size_t lds = ((size_t)BB_WAVES_PER_BLOCK << (8 + a.lphase)) * 4 + (cb < 8 ? 64 : 0);
     hipLaunchKernelGGL(k_count_states, dim3((unsigned)(g * a.nslot)), dim3(BB_BLOCK), lds, (hipStream_t)stream, a);
+    BB_HIP(hipGetLastError());
+    return BB_OK;
+}
+
+// ---- ... per time bin (k_state_bins.h) ----
+static int state_bins_params_check(const bb_states_params *p, uint64_t bin_rows)
+{
+    int rc = states_params_check(p);
+    if (rc) return rc;
+    if (bin_rows == 0 || bin_rows > 0x7fffffffull) return BB_EINVAL;          // a counter never exceeds bin_rows: int32 holds it
+    if ((bin_rows * (uint64_t)p->chunk * (uint64_t)p->bps) & 7) return BB_ENOTSUP;   // bins are whole bytes
+    if (((uint64_t)p->chunk << p->bps) > BB_BINS_MAX_PER_BIN) return BB_ENOTSUP;     // two bins fit a wave's window
+    return BB_OK;
+}
+
+int bb_count_states_bins_check(const bb_states_params *p, uint64_t bin_rows) { return state_bins_params_check(p, bin_rows); }
+
+#define BB_BINS_GRID 1280ull                         // workgroups: what 256 CUs hold at once with 32 KiB of LDS each
+
+int bb_count_states_bins(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size_t nframes,
+                         const bb_states_params *p, uint64_t bin_rows, uint64_t first_row, uint64_t nbins,
+                         uint32_t *d_counts, size_t ncounts, void *stream)
+{
+    int rc = state_bins_params_check(p, bin_rows);
+    if (rc) return rc;
+    if (!d_counts || ((uintptr_t)d_counts & 3)) return BB_EINVAL;
+    const uint64_t cb = (uint64_t)p->chunk * (uint64_t)p->bps;                // bits per row, at most 128
+    if (first_row > (1ull << 56)) return BB_ERANGE;
+    if (((first_row * cb) | ((p->row_lo & 7) * cb) | ((p->row_hi & 7) * cb)) & 7) return BB_ENOTSUP;   // whole bytes only
+    const uint64_t nc = (uint64_t)p->chunk << p->bps;                         // counters per bin and slot
+    if (nbins > (~0ull) / (nc * (uint64_t)p->nslot) || ncounts < nbins * nc * (uint64_t)p->nslot) return BB_ERANGE;
+    const uint64_t R = p->payload_nbytes * 8 / (uint64_t)p->bps / (uint64_t)p->chunk;
+    if (nframes && (R > (~0ull) / (uint64_t)nframes || p->payload_nbytes > (1ull << 62) / (uint64_t)nframes)) return BB_ERANGE;
+    if (p->row_hi > (uint64_t)nframes * R) return BB_ERANGE;
+    if (nframes == 0 || p->row_lo == p->row_hi) return BB_OK;
+    if (p->row_hi - p->row_lo > (~0ull) - first_row) return BB_ERANGE;
+    if ((first_row + (p->row_hi - 1 - p->row_lo)) / bin_rows >= nbins) return BB_ERANGE;   // the last counted row's bin
+    if (!d_buf || ((uintptr_t)d_buf & 3)) return BB_EINVAL;
+    const uint64_t nfs = (uint64_t)nframes * (uint64_t)p->nslot;
+    if (!d_src) {
+        rc = fixed_stride_check(p->src0, p->src_stride, 4, nfs, p->payload_nbytes, buf_nbytes);
+        if (rc) return rc;
+    }
+    bb_state_bins_args a;
+    a.buf = (const uint8_t *)d_buf;
+    a.src = d_src;
+    a.counts = d_counts;
+    a.src_lim = src_limit(buf_nbytes, p->payload_nbytes);
+    a.src0 = p->src0; a.src_stride = p->src_stride;
+    a.payload = p->payload_nbytes;
+    // rows -> bytes of a slot's stream (R * cb / 8 = payload: a frame begins on a byte)
+    a.lo_byte = (p->row_lo / R) * a.payload + (p->row_lo % R) * cb / 8;
+    a.hi_byte = (p->row_hi / R) * a.payload + (p->row_hi % R) * cb / 8;
+    a.first_byte = first_row * cb / 8;
+    a.bin_bytes = bin_rows * cb / 8;
+    a.nbins = nbins;
+    a.f_lo = a.lo_byte / a.payload;
+    a.nfr = (a.hi_byte + a.payload - 1) / a.payload - a.f_lo;               // frames that hold a counted byte
+    a.nslot = (uint32_t)p->nslot; a.chunk = (uint32_t)p->chunk; a.bps = (uint32_t)p->bps;
+    a.lnc = (uint32_t)ceil_log2((uint32_t)nc);
+    a.win_bins = BB_BINS_WIN >> a.lnc;
+    // work items: even pieces of at most BB_STATES_SEG bytes that meet no more bins than a window holds
+    uint64_t seg_max = BB_STATES_SEG;
+    if (a.bin_bytes < seg_max && (a.win_bins - 1) * a.bin_bytes < seg_max) seg_max = (a.win_bins - 1) * a.bin_bytes;
+    if (seg_max >= 16) {
+        seg_max &= ~15ull;
+        a.nseg = (a.payload + seg_max - 1) / seg_max;
+        a.seg_bytes = (uint32_t)((((a.payload + a.nseg - 1) / a.nseg) + 15) & ~15ull);
+    } else {
+        a.nseg = (a.payload + seg_max - 1) / seg_max;
+        a.seg_bytes = (uint32_t)seg_max;
+    }
+    if (a.nfr > (~0ull) / a.nseg || a.nfr * a.nseg > (~0ull) / a.nslot) return BB_ERANGE;
+    a.nwork = a.nfr * a.nseg * a.nslot;
+    // one contiguous run of items per wave, as many waves as the device holds at once
+    const uint64_t waves = std::min<uint64_t>(a.nwork, BB_BINS_GRID * BB_WAVES_PER_BLOCK);
+    a.per = (a.nwork + waves - 1) / waves;
+    const uint64_t runs = (a.nwork + a.per - 1) / a.per;
+    const uint64_t g = (runs + BB_WAVES_PER_BLOCK - 1) / BB_WAVES_PER_BLOCK;
+    hipLaunchKernelGGL(k_count_state_bins, dim3((unsigned)g), dim3(BB_BLOCK), 0, (hipStream_t)stream, a);
     BB_HIP(hipGetLastError());
     return BB_OK;
 }

@@ -592,6 +592,45 @@ def count_states(dbuf, nframes, payload_nbytes, bps, chunk=1, nslot=1, src=None,
     return counts
 
 
+STATES_BINS_MAX_COUNTERS = 1024    # chunk << bps the binned kernel takes (two bins in a wave's window on chip)
+
+
+def count_states_bins_supported(bps, chunk=1, bin_rows=8, nslot=1, payload_nbytes=None):
+    """Would `count_states_bins` take this geometry and bin length?  (bb_count_states_bins_check;
+    no device needed.)"""
+    if payload_nbytes is None:
+        payload_nbytes = max(4, chunk * bps // 8) if bps in (1, 2, 4, 8) else 4
+    if not 0 <= bin_rows < 1 << 64:
+        return False
+    return _lib.count_states_bins_check(bps, chunk, bin_rows, nslot, payload_nbytes) == _lib.BB_OK
+
+
+def count_states_bins(dbuf, nframes, payload_nbytes, bps, chunk, nslot, bin_rows, nbins, src=None, src0=0,
+                      src_stride=0, row_lo=0, row_hi=None, first_row=0, counts=None):
+    """Sampler statistics per time bin from packed bytes (bb_count_states_bins; EXTENSION):
+    as `count_states`, but counted row r goes to bin ``(first_row + r - row_lo) // bin_rows``
+    -> int32 device tensor of shape ``(nslot, nbins, chunk, 1 << bps)``.  Bins, `first_row`
+    and the row range are whole bytes of a slot's stream.  With `counts` (such a tensor,
+    contiguous) the call ADDS to it: windows of a file complete each other's bins.  Nothing
+    is decoded and nothing synchronises."""
+    p = _lib.StatesParams()
+    p.bps, p.chunk, p.nslot, p.reserved = bps, chunk, nslot, 0
+    p.payload_nbytes = payload_nbytes
+    p.src0, p.src_stride = src0, src_stride
+    if row_hi is None:
+        row_hi = nframes * (payload_nbytes * 8 // bps // chunk) if bps in (1, 2, 4, 8) and chunk > 0 else 0
+    p.row_lo, p.row_hi = row_lo, row_hi
+    if counts is None:
+        rc = lib.bb_count_states_bins_check(C.byref(p), bin_rows)     # (before a shape is made of the parameters)
+        check(rc, 'bb_count_states_bins')
+        counts = torch.zeros((nslot, nbins, chunk, 1 << bps), dtype=torch.int32, device=dbuf.device)
+    elif counts.dtype != torch.int32 or not counts.is_contiguous():
+        raise TypeError("counts must be a contiguous int32 tensor")
+    check(lib.bb_count_states_bins(_ptr(dbuf), dbuf.numel(), _ptr(src), nframes, C.byref(p), bin_rows, first_row,
+                                   nbins, _ptr(counts), counts.numel(), _stream(dbuf)), 'bb_count_states_bins')
+    return counts
+
+
 TOUCH_MIN_BYTES = 16 << 20
 def _touch_max_bytes():
     try:                                # (as the library reads it: csrc/bbdecode.hip touch_mib_default)

@@ -680,6 +680,39 @@ int bb_count_states(const void *d_buf, size_t buf_nbytes,
                     unsigned long long *d_counts, size_t ncounts, void *stream);
 int bb_count_states_check(const bb_states_params *params);
 
+/*
+ * The same counts as a time series: per thread slot, TIME BIN and position in a
+ * row.  Buffer, index, fixed stride, row_lo / row_hi and code order are those of
+ * bb_count_states.  Counted row r of the request has the series index
+ * g = first_row + (r - row_lo) and lands in bin g / bin_rows: a reader hands a
+ * file in window by window, and a bin that straddles two windows is completed
+ * by two calls.  Code c at position pos of a row of slot s in bin b ADDS one to
+ *     d_counts[(((s * nbins + b) * chunk + pos) << bps) + c]
+ * (uint32 counters, slot-major: the bins a wave finishes one after the other
+ * are contiguous memory; the caller zeroes them; bit-reproducible).  A counter
+ * of one call never exceeds bin_rows.
+ *
+ * bb_count_states_bins_check answers what the parameters alone decide:
+ * everything bb_count_states_check refuses, BB_EINVAL for bin_rows == 0 or
+ * bin_rows > 2^31 - 1, BB_ENOTSUP when bin_rows * chunk * bps is not a multiple
+ * of 8 (bins are whole bytes) or chunk << bps > 1024 (8-bit samples with chunk
+ * 8 and 16: two bins' counters must fit a wave's 8 KiB window on chip).
+ *
+ * The call itself answers in addition BB_ENOTSUP when first_row, row_lo or
+ * row_hi times chunk * bps is not a multiple of 8 (whole bytes only: there is
+ * no field-by-field edge), BB_ERANGE when ncounts < nslot * nbins * (chunk <<
+ * bps), when row_hi > nframes * R or when the last counted row's bin is >=
+ * nbins, BB_EINVAL when d_counts is NULL or not 4-byte aligned.  Stream-ordered,
+ * never allocates, never synchronises; nframes == 0 or row_lo == row_hi
+ * launches nothing; an argument error leaves d_counts untouched.
+ */
+int bb_count_states_bins(const void *d_buf, size_t buf_nbytes,
+                         const int64_t *d_src, size_t nframes,
+                         const bb_states_params *params,
+                         uint64_t bin_rows, uint64_t first_row, uint64_t nbins,
+                         uint32_t *d_counts, size_t ncounts, void *stream);
+int bb_count_states_bins_check(const bb_states_params *params, uint64_t bin_rows);
+
 /* ---- byte-aligned formats with an axis permutation --------------------- */
 
 /*
