@@ -46,3 +46,7 @@ def empty_output(shape, dtype=None, device=None):
 
 
 __all__ += ['empty_output']
+
+from .conversion import convert   # noqa: E402,F401
+
+__all__ += ['convert']

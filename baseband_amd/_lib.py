@@ -126,6 +126,16 @@ class StatesParams(C.Structure):
                 ('row_lo', C.c_uint64), ('row_hi', C.c_uint64)]
 
 
+class RepackParams(C.Structure):
+    _fields_ = [('bps', C.c_int32), ('coder_in', C.c_int32), ('coder_out', C.c_int32),
+                ('chunk_in', C.c_int32), ('nslot_in', C.c_int32), ('chunk_out', C.c_int32),
+                ('nslot_out', C.c_int32), ('fill_code', C.c_int32),
+                ('payload_in', C.c_uint64), ('payload_out', C.c_uint64),
+                ('src0', C.c_int64), ('src_stride', C.c_int64),
+                ('row_lo', C.c_uint64), ('row_hi', C.c_uint64), ('first_row', C.c_uint64),
+                ('reserved', C.c_uint64)]
+
+
 class Mark4ScanParams(C.Structure):
     _fields_ = [('first_offset', C.c_uint64), ('ntrack', C.c_int32),
                 ('ref_year', C.c_int32), ('ref_qms', C.c_int64),
@@ -214,6 +224,8 @@ SIGNATURES = [
     ('bb_count_states_bins', C.c_int, [_vp, _sz, _vp, _sz, C.POINTER(StatesParams), C.c_uint64, C.c_uint64,
                                        C.c_uint64, _vp, _sz, _vp]),
     ('bb_count_states_bins_check', C.c_int, [C.POINTER(StatesParams), C.c_uint64]),
+    ('bb_repack_frames', C.c_int, [_vp, _sz, _vp, _sz, C.POINTER(RepackParams), _vp, _sz, _vp]),
+    ('bb_repack_check', C.c_int, [C.POINTER(RepackParams)]),
     ('bb_fetch_counter', C.c_int, [_vp, _vp, _vp, _vp]),
     ('bb_mark5b_read_window', C.c_int, [_vp, _sz, C.POINTER(Mark5BScanParams), _sz, _sz, C.POINTER(DecodeParams),
                                         _vp, C.c_int, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
@@ -299,6 +311,25 @@ def count_states_bins_check(bps, chunk=1, bin_rows=8, nslot=1, payload_nbytes=4,
     p.bps, p.chunk, p.nslot, p.reserved = bps, chunk, nslot, reserved
     p.payload_nbytes, p.row_lo, p.row_hi = payload_nbytes, row_lo, row_hi
     return lib.bb_count_states_bins_check(C.byref(p), bin_rows)
+
+
+def repack_params(bps, coder_in, coder_out, chunk_in, nslot_in, chunk_out, nslot_out, payload_in, payload_out,
+                  fill_code=0, src0=0, src_stride=0, row_lo=0, row_hi=0, first_row=0, reserved=0):
+    p = RepackParams()
+    p.bps, p.coder_in, p.coder_out, p.fill_code = bps, coder_in, coder_out, fill_code
+    p.chunk_in, p.nslot_in, p.chunk_out, p.nslot_out = chunk_in, nslot_in, chunk_out, nslot_out
+    p.payload_in, p.payload_out, p.src0, p.src_stride = payload_in, payload_out, src0, src_stride
+    p.row_lo, p.row_hi, p.first_row, p.reserved = row_lo, row_hi, first_row, reserved
+    return p
+
+
+def repack_check(bps, coder_in, coder_out, chunk_in, nslot_in, chunk_out, nslot_out, payload_in, payload_out,
+                 fill_code=0, row_lo=0, row_hi=0, first_row=0, reserved=0):
+    """What `bb_repack_frames` would answer to these parameters, as far as they decide it
+    (bb_repack_check: no buffers, no device): BB_OK, BB_EINVAL or BB_ENOTSUP."""
+    p = repack_params(bps, coder_in, coder_out, chunk_in, nslot_in, chunk_out, nslot_out, payload_in, payload_out,
+                      fill_code, 0, 0, row_lo, row_hi, first_row, reserved)
+    return lib.bb_repack_check(C.byref(p))
 
 
 def out_type_of(dtype):

@@ -1195,6 +1195,135 @@ class GPUStreamReaderBase:
             power, valid = power.sum(-1), valid[..., 0]
         return power / valid.double()
 
+    # -- format conversion on the packed bytes (kernels.repack_frames; baseband_amd.convert)
+    def _walk_packed(self, first, last, visit):
+        """``visit(dbuf, src, s, e)`` for the frame sets [first, last) in pieces [s, e): the
+        packed bytes of a piece on the device and its index of payload offsets into them
+        (-1: missing or invalid).  The three ways `state_counts` gets at the bytes: a
+        re-located index, resident bytes, or a `WindowPipeline` over the file image with
+        the un-fused scan and index."""
+        nslot = self._states_geometry()[3]
+        set_nbytes = self._set_nbytes
+        located = getattr(self, '_resident', None)
+        resident = self._resident_bytes()
+        if located is not None:
+            dev, src = located
+            visit(dev, src[first * nslot:last * nslot].contiguous(), first, last)
+        elif resident is not None:
+            lo = min(self._file_offset0 + first * set_nbytes, resident.numel())
+            hi = max(lo, min(self._file_offset0 + last * set_nbytes, resident.numel()))
+            win = self._device_window(resident, lo, hi)
+            visit(win, self._states_index(win, first, last - first), first, last)
+        else:
+            image = self._image()
+            per_win = min(last - first, max(1, self.window_bytes // set_nbytes))
+            pipe = WindowPipeline(image, per_win * set_nbytes)
+            ranges, spans = [], []
+            for s in range(first, last, per_win):
+                e = min(last, s + per_win)
+                lo = min(self._file_offset0 + s * set_nbytes, len(image))
+                ranges.append((lo, max(lo, min(self._file_offset0 + e * set_nbytes, len(image)))))
+                spans.append((s, e))
+
+            def process(dbuf, i):
+                s, e = spans[i]
+                win = self._device_window(dbuf, 0, dbuf.numel())
+                visit(win, self._states_index(win, s, e - s), s, e)
+
+            pipe.run(ranges, process)
+            pipe.release()
+
+    def _packed_request(self, count):
+        if self.closed:
+            raise ValueError("I/O operation on closed stream.")
+        if self._states_geometry() is None:
+            raise NotImplementedError("{} has no packed reads".format(type(self).__name__))
+        if count < 0 or count > self.shape[0] - self.offset:
+            raise EOFError("cannot read from beyond end of input.")
+
+    def _mark_invalid(self, marks, src, s, e, start, stop, spf_out):
+        """Add to `marks` (int32 device tensor, one more entry than output frames: a
+        difference array) the output frames that draw from a frame set of [s, e) with an
+        index entry below 0."""
+        nslot = self._states_geometry()[3]
+        spf = self.samples_per_frame
+        bad = torch.nonzero((src.reshape(e - s, nslot) < 0).any(1)).reshape(-1) + s
+        lo = torch.clamp(bad * spf, min=start) - start
+        hi = torch.clamp((bad + 1) * spf, max=stop) - 1 - start
+        one = torch.ones_like(bad, dtype=torch.int32)
+        marks.index_add_(0, torch.div(lo, spf_out, rounding_mode='floor'), one)
+        marks.index_add_(0, torch.div(hi, spf_out, rounding_mode='floor') + 1, -one)
+
+    def frames_valid(self, count, samples_per_frame):
+        """Host bool array, one entry per frame of `samples_per_frame` samples that the
+        next `count` samples from the current offset make up (the last one may be short):
+        true when every frame-slot of this stream the frame draws from is there and valid.
+        From the headers alone (scan and index); nothing is decoded, the offset stays."""
+        if self.closed:
+            raise ValueError("I/O operation on closed stream.")
+        if count < 0 or count > self.shape[0] - self.offset:
+            raise EOFError("cannot read from beyond end of input.")
+        nout = -(-count // samples_per_frame)
+        if self._states_geometry() is None or count == 0:   # (no index of payloads: nothing known to be missing)
+            return np.ones(nout, bool)
+        kernels.require_gpu()
+        spf = self.samples_per_frame
+        start, stop = self.offset, self.offset + count
+        marks = torch.zeros(nout + 1, dtype=torch.int32, device='cuda')
+        self._walk_packed(start // spf, -(-stop // spf),
+                          lambda dbuf, src, s, e: self._mark_invalid(marks, src, s, e, start, stop, samples_per_frame))
+        return (torch.cumsum(marks, 0)[:nout] == 0).cpu().numpy()
+
+    def read_packed(self, count, coder, nthread, nchan, samples_per_frame, fill_code):
+        """The next `count` samples as packed payloads of another frame geometry, without
+        decoding them (bb_repack_frames) -> ``(payloads, valid)``: a uint8 device tensor of
+        shape ``(count // samples_per_frame, nthread, payload_nbytes)`` holding what a
+        stream writer of `coder` (``_lib.CODER_*``) with `nthread` threads of `nchan`
+        channels and `samples_per_frame` samples per frame would encode ``read(count)``
+        to, and a host bool array, true where every frame-slot of this stream that an
+        output frame draws from is there and valid.  Samples of the others hold
+        `fill_code`.  `count` is a whole number of output frames; the offset must lie on a
+        byte boundary of a thread's stream on both sides.  Threads follow the reader's
+        selection; a channel `subset` is not applied.  Advances the offset."""
+        count = operator.index(count)
+        self._packed_request(count)
+        coder_in, bps, chunk_in, nslot_in, payload_in = self._states_geometry()
+        chunk_out = nchan * (2 if self.complex_data else 1)
+        if count % samples_per_frame:
+            raise ValueError("read_packed: count must be a whole number of frames of {} samples"
+                             .format(samples_per_frame))
+        if samples_per_frame * chunk_out * bps % 32:
+            raise ValueError("read_packed: payloads are whole 32-bit words")
+        payload_out = samples_per_frame * chunk_out * bps // 8
+        if not kernels.repack_supported(bps, coder_in, coder, chunk_in, nslot_in, chunk_out, nthread,
+                                        payload_in, payload_out):
+            raise NotImplementedError(
+                "read_packed: {} x {} codes of {} bits (coder {}) -> {} x {} (coder {}) is not a conversion the "
+                "repack kernel takes".format(nslot_in, chunk_in, bps, coder_in, nthread, chunk_out, coder))
+        whole = max(1, 8 // (min(chunk_in, chunk_out) * bps))       # samples in a byte of a thread's stream
+        if self.offset % whole:
+            raise ValueError("read_packed: whole bytes only: seek to a multiple of {} samples".format(whole))
+        kernels.require_gpu()
+        nout = count // samples_per_frame
+        out = torch.empty((nout, nthread, payload_out), dtype=torch.uint8, device='cuda')
+        if count == 0:
+            return out, np.ones(0, bool)
+        spf = self.samples_per_frame
+        start, stop = self.offset, self.offset + count
+        marks = torch.zeros(nout + 1, dtype=torch.int32, device='cuda')
+
+        def visit(dbuf, src, s, e):
+            lo = max(start, s * spf)
+            kernels.repack_frames(dbuf, e - s, payload_in, bps, coder_in, chunk_in, nslot_in, coder, chunk_out,
+                                  nthread, payload_out, fill_code=fill_code, src=src, row_lo=lo - s * spf,
+                                  row_hi=min(stop, e * spf) - s * spf, first_row=lo - start, out=out.reshape(-1))
+            self._mark_invalid(marks, src, s, e, start, stop, samples_per_frame)
+
+        self._walk_packed(start // spf, -(-stop // spf), visit)
+        valid = (torch.cumsum(marks, 0)[:nout] == 0).cpu().numpy()
+        self.offset += count
+        return out, valid
+
     # ``host_results = True``: ``read()`` without `out` returns NEW NumPy arrays, as the
     # reference does (what the ``baseband.io`` plugin modules switch on): arrays on pinned
     # memory filled by the DMA engine (`staging.download_new`), and -- in loops of small

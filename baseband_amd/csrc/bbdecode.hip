@@ -14,6 +14,7 @@
 #include "k_copy.h"
 #include "k_states.h"
 #include "k_state_bins.h"
+#include "k_repack.h"
 #include "k_tfpick.h"
 #if BB_EXP
 #include "k_burst.h"
@@ -1717,6 +1718,97 @@ int bb_count_states_bins(const void *d_buf, size_t buf_nbytes, const int64_t *d_
     const uint64_t runs = (a.nwork + a.per - 1) / a.per;
     const uint64_t g = (runs + BB_WAVES_PER_BLOCK - 1) / BB_WAVES_PER_BLOCK;
     hipLaunchKernelGGL(k_count_state_bins, dim3((unsigned)g), dim3(BB_BLOCK), 0, (hipStream_t)stream, a);
+    BB_HIP(hipGetLastError());
+    return BB_OK;
+}
+
+// ---- format conversion on the packed bytes (k_repack.h): decode and encode of
+//      base/payload.py:314-330, vdif/payload.py:25-114, mark5b/payload.py:27-106 back to back ----
+// The code map of a coder pair at `bps`: 0 identity, 1 invert every bit, 2 swap the two bits of a field; -1: none.
+static int repack_code_map(int coder_in, int coder_out, int bps)
+{
+    if (!coder_supported(coder_in, bps) || !coder_supported(coder_out, bps)) return -1;
+    if (coder_in == coder_out) return 0;
+    const bool vm = (coder_in == BB_CODER_VDIF && coder_out == BB_CODER_MARK5B) ||
+                    (coder_in == BB_CODER_MARK5B && coder_out == BB_CODER_VDIF);
+    if (vm && bps == 1) return 1;
+    if (vm && bps == 2) return 2;
+    return -1;                                              // VDIF <-> INT needs rescaling
+}
+
+static int repack_params_check(const bb_repack_params *p)
+{
+    if (!p) return BB_EINVAL;
+    if (log2_bps(p->bps) < 0) return BB_ENOTSUP;
+    if (p->reserved != 0 || p->chunk_in < 1 || p->nslot_in < 1 || p->chunk_out < 1 || p->nslot_out < 1) return BB_EINVAL;
+    if (repack_code_map(p->coder_in, p->coder_out, p->bps) < 0) return BB_ENOTSUP;
+    if ((p->chunk_in & (p->chunk_in - 1)) || (p->nslot_in & (p->nslot_in - 1)) ||
+        (p->chunk_out & (p->chunk_out - 1)) || (p->nslot_out & (p->nslot_out - 1))) return BB_ENOTSUP;
+    if ((int64_t)p->nslot_in * p->chunk_in != (int64_t)p->nslot_out * p->chunk_out) return BB_EINVAL;
+    if ((uint32_t)p->nslot_in > BB_REPACK_MAX_SLOTS || (uint32_t)p->nslot_out > BB_REPACK_MAX_SLOTS) return BB_ENOTSUP;
+    if ((int64_t)p->nslot_in * p->chunk_in * p->bps > (int64_t)BB_REPACK_MAX_ROW_BITS) return BB_ENOTSUP;
+    if (p->payload_in == 0 || (p->payload_in & 3) || p->payload_in > (1ull << 56)) return BB_EINVAL;
+    if (p->payload_out == 0 || (p->payload_out & 3) || p->payload_out > (1ull << 56)) return BB_EINVAL;
+    if ((p->payload_in * 8 / (uint64_t)p->bps) % (uint64_t)p->chunk_in) return BB_EINVAL;     // whole rows
+    if ((p->payload_out * 8 / (uint64_t)p->bps) % (uint64_t)p->chunk_out) return BB_EINVAL;
+    if (p->fill_code < 0 || p->fill_code >= (1 << p->bps)) return BB_EINVAL;
+    if (p->row_lo > p->row_hi) return BB_EINVAL;
+    return BB_OK;
+}
+
+int bb_repack_check(const bb_repack_params *p) { return repack_params_check(p); }
+
+#define BB_REPACK_GRID 4096ull                       // workgroups: several rounds of what 256 CUs hold (4 each, 37 KiB of LDS)
+
+int bb_repack_frames(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size_t nframes,
+                     const bb_repack_params *p, void *d_out, size_t out_nbytes, void *stream)
+{
+    int rc = repack_params_check(p);
+    if (rc) return rc;
+    if (!d_out || ((uintptr_t)d_out & 15)) return BB_EINVAL;
+    const uint64_t bi = (uint64_t)p->chunk_in * (uint64_t)p->bps, bo = (uint64_t)p->chunk_out * (uint64_t)p->bps;   // bits per row and slot
+    if (p->first_row > (1ull << 56)) return BB_ERANGE;
+    if ((((p->row_lo & 7) | (p->row_hi & 7) | (p->first_row & 7)) * (bi | bo)) & 7) return BB_ENOTSUP;   // whole bytes only (bi, bo are powers of two)
+    const uint64_t R_in = p->payload_in * 8 / bi, R_out = p->payload_out * 8 / bo;
+    if (nframes && (R_in > (~0ull) / (uint64_t)nframes || p->payload_in > (1ull << 58) / (uint64_t)nframes)) return BB_ERANGE;
+    if (p->row_hi > (uint64_t)nframes * R_in) return BB_ERANGE;
+    if (nframes == 0 || p->row_lo == p->row_hi) return BB_OK;
+    const uint64_t nrows = p->row_hi - p->row_lo;
+    const uint64_t g_last = p->first_row + (nrows - 1);                       // the last output row, in slot nslot_out - 1
+    const uint64_t f_last = g_last / R_out;
+    if (f_last >= (1ull << 58) / (p->payload_out * (uint64_t)p->nslot_out)) return BB_ERANGE;
+    if ((f_last * (uint64_t)p->nslot_out + (uint64_t)p->nslot_out - 1) * p->payload_out + ((g_last % R_out + 1) * bo + 7) / 8 > out_nbytes)
+        return BB_ERANGE;
+    if (!d_buf || ((uintptr_t)d_buf & 3)) return BB_EINVAL;
+    if (!d_src) {
+        rc = fixed_stride_check(p->src0, p->src_stride, 4, (uint64_t)nframes * (uint64_t)p->nslot_in, p->payload_in, buf_nbytes);
+        if (rc) return rc;
+    }
+    bb_repack_args a;
+    a.buf = (const uint8_t *)d_buf;
+    a.src = d_src;
+    a.out = (uint8_t *)d_out;
+    a.buf_n = buf_nbytes;
+    a.src_lim = src_limit(buf_nbytes, p->payload_in);
+    a.src0 = p->src0; a.src_stride = p->src_stride;
+    a.pay_in = p->payload_in; a.pay_out = p->payload_out;
+    a.row_lo = p->row_lo; a.first_row = p->first_row; a.nrows = nrows;
+    a.R_out = R_out;
+    a.F0 = p->first_row / R_out;
+    a.nslot_in = (uint32_t)p->nslot_in; a.nslot_out = (uint32_t)p->nslot_out;
+    a.lbi = ceil_log2(bi); a.lbo = ceil_log2(bo);
+    a.T = BB_REPACK_ITEM_BITS / (uint32_t)(bi * a.nslot_in);                  // at least 256 rows: 16 bytes or more of every slot
+    a.sstride = ((a.T << a.lbi) >> 3) + BB_REPACK_SLACK;
+    a.nseg = (R_out + a.T - 1) / a.T;
+    const uint64_t nf = f_last - a.F0 + 1;
+    if (nf > (~0ull) / a.nseg) return BB_ERANGE;
+    a.nwork = nf * a.nseg;
+    a.map = (uint32_t)repack_code_map(p->coder_in, p->coder_out, p->bps);
+    a.fillw = (uint32_t)p->fill_code * (0xffffffffu / ((1u << p->bps) - 1u));
+    // chunks of min(bi, bo) bits stay together; equal slot structures are a stream of whole dwords
+    a.lg = a.lbi == a.lbo ? 5u : std::min(5u, std::min(a.lbi, a.lbo));
+    const dim3 grid = capped_grid((a.nwork + BB_WAVES_PER_BLOCK - 1) / BB_WAVES_PER_BLOCK, BB_REPACK_GRID);
+    hipLaunchKernelGGL(k_repack, grid, dim3(BB_BLOCK), 0, (hipStream_t)stream, a);
     BB_HIP(hipGetLastError());
     return BB_OK;
 }

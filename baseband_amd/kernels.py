@@ -631,6 +631,50 @@ def count_states_bins(dbuf, nframes, payload_nbytes, bps, chunk, nslot, bin_rows
     return counts
 
 
+REPACK_MAX_ROW_BITS = 256      # nslot * chunk * bps the repack kernel takes
+REPACK_MAX_SLOTS = 32          # ... and thread slots on either side
+
+
+def repack_supported(bps, coder_in, coder_out, chunk_in, nslot_in, chunk_out, nslot_out,
+                     payload_in=None, payload_out=None):
+    """Would `repack_frames` take this conversion?  (bb_repack_check; no device needed.)"""
+    ok = bps in (1, 2, 4, 8)
+    if payload_in is None:
+        payload_in = max(4, chunk_in * bps // 8) if ok and chunk_in > 0 else 4
+    if payload_out is None:
+        payload_out = max(4, chunk_out * bps // 8) if ok and chunk_out > 0 else 4
+    return _lib.repack_check(bps, coder_in, coder_out, chunk_in, nslot_in, chunk_out, nslot_out,
+                             payload_in, payload_out) == _lib.BB_OK
+
+
+def repack_frames(dbuf, nframes, payload_in, bps, coder_in, chunk_in, nslot_in, coder_out, chunk_out, nslot_out,
+                  payload_out, fill_code=0, src=None, src0=0, src_stride=0, row_lo=0, row_hi=None, first_row=0,
+                  out=None):
+    """Format conversion on the packed bytes (bb_repack_frames): rows [row_lo, row_hi) of
+    `nframes` input frame(set)s of `nslot_in` payloads with `chunk_in` codes per row, taken
+    through the index `src` (-1 or an offset outside the buffer: `fill_code`) or at ``src0 +
+    k * src_stride``, become output rows ``first_row + (r - row_lo)`` of payloads of
+    `nslot_out` slots with `chunk_out` codes per row, codes mapped from `coder_in` to
+    `coder_out` -> uint8 device tensor of whole output frames, payload (F, t) at ``(F *
+    nslot_out + t) * payload_out``.  With `out` (such a tensor, contiguous) only the bytes
+    of the rows written change.  The row range and `first_row` are whole bytes of every
+    slot stream.  Nothing is decoded and nothing synchronises."""
+    if row_hi is None:
+        row_hi = nframes * (payload_in * 8 // bps // chunk_in) if bps in (1, 2, 4, 8) and chunk_in > 0 else 0
+    p = _lib.repack_params(bps, coder_in, coder_out, chunk_in, nslot_in, chunk_out, nslot_out, payload_in,
+                           payload_out, fill_code, src0, src_stride, row_lo, row_hi, first_row)
+    if out is None:
+        check(lib.bb_repack_check(C.byref(p)), 'bb_repack_frames')   # (before a shape is made of the parameters)
+        r_out = payload_out * 8 // bps // chunk_out
+        nout = -(-(first_row + row_hi - row_lo) // r_out)
+        out = torch.empty(nout * nslot_out * payload_out, dtype=torch.uint8, device=dbuf.device)
+    elif out.dtype != torch.uint8 or not out.is_contiguous():
+        raise TypeError("out must be a contiguous uint8 tensor")
+    check(lib.bb_repack_frames(_ptr(dbuf), dbuf.numel(), _ptr(src), nframes, C.byref(p),
+                               _ptr(out), out.numel(), _stream(dbuf)), 'bb_repack_frames')
+    return out
+
+
 TOUCH_MIN_BYTES = 16 << 20
 def _touch_max_bytes():
     try:                                # (as the library reads it: csrc/bbdecode.hip touch_mib_default)

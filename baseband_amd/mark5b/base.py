@@ -295,9 +295,15 @@ class Mark5BStreamWriter(GPUStreamWriterBase):
         self._start_time = header0.get_time(frame_rate=frame_rate)
 
     def _write_frames(self, data, valid):
-        nfr = data.shape[0] // self.samples_per_frame
-        packed = kernels.encode_flat(data, _lib.CODER_MARK5B, self.bps).reshape(nfr, 10000)
-        valid = np.asarray(valid, bool)
+        self._write_packed(kernels.encode_flat(data, _lib.CODER_MARK5B, self.bps), valid)
+
+    def _write_packed(self, packed, valid):
+        """Frames whose payloads are packed already (device uint8, frame / byte; the writer's
+        own to change): the fill pattern in the frames `valid` says no to, headers, and out
+        to the file."""
+        nfr = packed.numel() // 10000
+        packed = packed.reshape(nfr, 10000)
+        valid = np.broadcast_to(np.asarray(valid, bool), (nfr,))
         if not valid.all():             # invalid frames carry the fill pattern
             bad = torch.from_numpy(np.nonzero(~valid)[0]).to(packed.device)
             packed.view(torch.int32)[bad] = 0x11223344

@@ -791,7 +791,13 @@ class VDIFStreamWriter(GPUStreamWriterBase):
         nsets = data.shape[0] // spf
         # (set, sample, thread, chan) -> (set, thread, sample, chan): payload order
         block = data.reshape(nsets, spf, nthread, nchan).permute(0, 2, 1, 3).contiguous()
-        packed = kernels.encode_flat(block, self._coder, self.bps)
+        self._write_packed(kernels.encode_flat(block, self._coder, self.bps), valid)
+
+    def _write_packed(self, packed, valid):
+        """Frame sets whose payloads are packed already (device uint8, set / thread / byte):
+        headers, the invalid bit of the sets `valid` says no to, and out to the file."""
+        nthread = self._unsliced_shape[0]
+        nsets = packed.numel() // (nthread * self.header0.payload_nbytes)
         h = self.header0.copy()
         idx = self.header0['frame_nr'] + self._nframes_written
         h['seconds'] = self.header0['seconds'] + idx // self._frame_rate

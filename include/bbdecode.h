@@ -713,6 +713,78 @@ int bb_count_states_bins(const void *d_buf, size_t buf_nbytes,
                          uint32_t *d_counts, size_t ncounts, void *stream);
 int bb_count_states_bins_check(const bb_states_params *params, uint64_t bin_rows);
 
+/* ---- format conversion on the packed bytes -------------------------------- */
+
+/*
+ * Decode of one format and encode of another applied back to back, without the
+ * floats in between: base/payload.py:314-330 (fromdata / data) with
+ * vdif/payload.py:25-114 and mark5b/payload.py:27-106.  Samples of the same
+ * size have the same scale in these formats (docs/tutorials/
+ * using_baseband.rst:589-591), so decode-then-encode is an exact map from code
+ * to code:
+ *     same coder (VDIF, Mark 5B, INT), every bps it has     identity
+ *     VDIF <-> Mark 5B, 1 bit                               0 <-> 1
+ *     VDIF <-> Mark 5B, 2 bits                              {0, 2, 1, 3}
+ * Every other pair (VDIF <-> INT needs rescaling) is BB_ENOTSUP.
+ *
+ * Input as for bb_decode_frames and bb_count_states: frame-slot (f, s) of the
+ * request has its payload_in bytes at d_src[f * nslot_in + s] (-1, any negative
+ * offset or a payload not wholly inside the buffer: a source that counts
+ * nothing) or, with d_src == NULL, at src0 + (f * nslot_in + s) * src_stride
+ * (multiples of 4; the last payload inside the buffer, else BB_ERANGE).  Fields
+ * are taken LSB first.  With R_in = payload_in * 8 / bps / chunk_in rows per
+ * frame, component k = s * chunk_in + p of input row r has the code c in field
+ * (r % R_in) * chunk_in + p of payload (r / R_in, s).  The output is a
+ * contiguous buffer of payloads only, payload (F, t) at (F * nslot_out + t) *
+ * payload_out, the payload order of the VDIF writer (vdif/base.py:792-794;
+ * Mark 5B's for nslot_out == 1).  Counted row r in [row_lo, row_hi) has the
+ * output row G = first_row + (r - row_lo), and with t = k / chunk_out,
+ * q = k % chunk_out
+ *     field (G % R_out) * chunk_out + q of output payload (G / R_out, t) = map[c]
+ * or fill_code (not mapped) where the source counts nothing.  Nothing outside
+ * the buffer is read; output bytes outside the rows written are not touched, so
+ * one request may be split over several calls into one output buffer.
+ *
+ * row_lo, row_hi and first_row must fall on a byte boundary of every input and
+ * every output slot stream (times chunk_in * bps and times chunk_out * bps a
+ * multiple of 8), else BB_ENOTSUP: whole bytes only, there is no field-by-field
+ * edge.  BB_ERANGE: row_hi > nframes * R_in, the last output row beyond
+ * out_nbytes, the last fixed-stride payload outside the buffer.  BB_EINVAL:
+ * NULL pointers, d_buf not 4-byte or d_out not 16-byte aligned, and what
+ * bb_repack_check answers with it.  Stream-ordered, never allocates, never
+ * synchronises; nframes == 0 or row_lo == row_hi launches nothing; an argument
+ * error leaves d_out untouched.
+ *
+ * bb_repack_check answers what the parameters alone decide (no buffers, no
+ * device): BB_EINVAL (a NULL block, reserved != 0, counts below 1, payloads
+ * that are 0, not multiples of 4 or not whole rows, row_lo > row_hi, nslot_in *
+ * chunk_in != nslot_out * chunk_out, fill_code outside [0, 1 << bps)),
+ * BB_ENOTSUP (bps not in {1, 2, 4, 8}, a coder pair outside the table above,
+ * chunks or slot counts that are not powers of two, more than 32 slots on a
+ * side, a row of more than 256 bits).  Every power-of-two geometry with rows of
+ * at most 256 bits and at most 32 slots on either side is BB_OK.
+ */
+typedef struct bb_repack_params {
+    int32_t  bps;               /* 1, 2, 4, 8: the same on both sides */
+    int32_t  coder_in, coder_out;
+    int32_t  chunk_in;          /* codes per (sample, slot) of the input; a power of two */
+    int32_t  nslot_in;          /* thread slots of the input; a power of two */
+    int32_t  chunk_out, nslot_out;
+    int32_t  fill_code;         /* code of the OUTPUT coder written where a source counts nothing */
+    uint64_t payload_in;        /* bytes per frame and slot; multiples of 4; whole rows */
+    uint64_t payload_out;
+    int64_t  src0, src_stride;  /* used when d_src == NULL, as in bb_decode_frames */
+    uint64_t row_lo, row_hi;    /* rows [row_lo, row_hi) of the request's nframes * R_in */
+    uint64_t first_row;         /* output row of row_lo */
+    uint64_t reserved;          /* 0 */
+} bb_repack_params;
+
+int bb_repack_frames(const void *d_buf, size_t buf_nbytes,
+                     const int64_t *d_src, size_t nframes,
+                     const bb_repack_params *params,
+                     void *d_out, size_t out_nbytes, void *stream);
+int bb_repack_check(const bb_repack_params *params);
+
 /* ---- byte-aligned formats with an axis permutation --------------------- */
 
 /*
