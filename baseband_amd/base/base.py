@@ -381,6 +381,20 @@ class _FileReaderInfoProperty:
 VLBIFileReaderBase.info = _FileReaderInfoProperty()
 
 
+class _WalkVerdict:
+    """What a walk over packed bytes at the fixed stride learns about its frames
+    (`GPUStreamReaderBase._walk_packed`): a device counter that bb_verify_records adds to,
+    and the frames the file's bytes did not reach (known on the host)."""
+    __slots__ = ('counter', 'missing')
+
+    def __init__(self):
+        self.counter = torch.zeros(1, dtype=torch.int32, device='cuda')
+        self.missing = 0
+
+    def nbad(self):
+        return self.missing + int(self.counter.item())
+
+
 def _to_host_array(data, out):
     """Device tensor -> the caller's NumPy `out`: pinned double-buffered copy
     for large contiguous destinations, plain copy otherwise."""
@@ -1024,7 +1038,15 @@ class GPUStreamReaderBase:
         decoded and the offset does not move.  Samples of frames that ``read()`` would
         fill (missing or invalid ones) are left out; bad frames do not raise.  Threads
         follow the reader's selection; a channel `subset` is NOT applied: counting
-        every channel costs nothing more."""
+        every channel costs nothing more.
+
+        A file that lost bytes or frames is counted as ``read()`` under ``verify='fix'``
+        reads it, whatever has been read before: when the pass meets headers that are
+        missing or off the fixed stride, the frames are located byte by byte
+        (`_relocate`, as a read would) and the whole request is counted again through
+        that index.  A ``verify=True`` reader gives the same counts and stays strict:
+        the index is used for the statistics only.  ``verify=False`` counts what stands
+        at the fixed stride."""
         if self.closed:
             raise ValueError("I/O operation on closed stream.")
         geom = self._states_geometry()
@@ -1035,55 +1057,28 @@ class GPUStreamReaderBase:
             raise NotImplementedError(
                 "state_counts: a complete sample of {} codes x {} bits is not one the counting kernel "
                 "takes (a power of two of codes, chunk * bps <= {})".format(chunk, bps, kernels.STATES_MAX_ROW_BITS))
-        samples_left = self.shape[0] - self.offset
-        if count is None or count < 0:
-            count = max(0, samples_left)
-        if count > samples_left:
-            raise EOFError("cannot read from beyond end of input.")
-        kernels.require_gpu()
-        counts = torch.zeros((nslot, chunk, 1 << bps), dtype=torch.int64, device='cuda')
-        if count == 0:
-            return self._states_shape(counts)
-        spf = self.samples_per_frame
-        start, stop = self.offset, self.offset + count
-        first, last = start // spf, -(-stop // spf)
-        set_nbytes = self._set_nbytes
 
-        def add(dbuf, src, s, e):
-            kernels.count_states(dbuf, e - s, payload, bps, chunk, nslot, src=src,
-                                 row_lo=max(start, s * spf) - s * spf, row_hi=min(stop, e * spf) - s * spf,
-                                 counts=counts)
+        def answer():
+            samples_left = self.shape[0] - self.offset
+            n = max(0, samples_left) if count is None or count < 0 else count
+            if n > samples_left:
+                raise EOFError("cannot read from beyond end of input.")
+            kernels.require_gpu()
+            counts = torch.zeros((nslot, chunk, 1 << bps), dtype=torch.int64, device='cuda')
+            if n == 0:
+                return self._states_shape(counts), 0
+            spf = self.samples_per_frame
+            start, stop = self.offset, self.offset + n
 
-        located = getattr(self, '_resident', None)
-        resident = self._resident_bytes()
-        if located is not None:
-            # a re-located index (bytes went missing): offsets into the whole file in HBM
-            dev, src = located
-            add(dev, src[first * nslot:last * nslot].contiguous(), first, last)
-        elif resident is not None:
-            lo = min(self._file_offset0 + first * set_nbytes, resident.numel())
-            hi = max(lo, min(self._file_offset0 + last * set_nbytes, resident.numel()))
-            win = self._device_window(resident, lo, hi)
-            add(win, self._states_index(win, first, last - first), first, last)
-        else:
-            image = self._image()
-            per_win = min(last - first, max(1, self.window_bytes // set_nbytes))
-            pipe = WindowPipeline(image, per_win * set_nbytes)
-            ranges, spans = [], []
-            for s in range(first, last, per_win):
-                e = min(last, s + per_win)
-                lo = min(self._file_offset0 + s * set_nbytes, len(image))
-                ranges.append((lo, max(lo, min(self._file_offset0 + e * set_nbytes, len(image)))))
-                spans.append((s, e))
+            def add(dbuf, src, s, e):
+                kernels.count_states(dbuf, e - s, payload, bps, chunk, nslot, src=src,
+                                     row_lo=max(start, s * spf) - s * spf, row_hi=min(stop, e * spf) - s * spf,
+                                     counts=counts)
 
-            def process(dbuf, i):
-                s, e = spans[i]
-                win = self._device_window(dbuf, 0, dbuf.numel())
-                add(win, self._states_index(win, s, e - s), s, e)
+            nbad = self._walk_packed(start // spf, -(-stop // spf), add)
+            return self._states_shape(counts), nbad
 
-            pipe.run(ranges, process)
-            pipe.release()
-        return self._states_shape(counts)
+        return self._answer_packed(answer)
 
     def state_series(self, bin_samples, count=None):
         """`state_counts` as a time series: int32 device tensor of shape ``(nbins,) +
@@ -1095,7 +1090,8 @@ class GPUStreamReaderBase:
         code axis is its number of valid samples, and ``state_series(n, count).sum(0)``
         equals ``state_counts(count)``.  Bins are whole bytes of a thread's stream:
         `bin_samples`, the offset and `count` must be multiples of ``8 / (codes per sample
-        * bps)`` samples where that is more than one."""
+        * bps)`` samples where that is more than one.  Damaged files and ``verify=True``
+        readers: as `state_counts` -- the frames are located, bad frames do not raise."""
         if self.closed:
             raise ValueError("I/O operation on closed stream.")
         geom = self._states_geometry()
@@ -1113,80 +1109,51 @@ class GPUStreamReaderBase:
                 "state_series: a complete sample of {} codes x {} bits is not one the binned counting kernel "
                 "takes (a power of two of codes, chunk * bps <= {}, chunk << bps <= {})".format(
                     chunk, bps, kernels.STATES_MAX_ROW_BITS, kernels.STATES_BINS_MAX_COUNTERS))
-        samples_left = self.shape[0] - self.offset
-        if count is None or count < 0:
-            count = max(0, samples_left)
-        if count > samples_left:
-            raise EOFError("cannot read from beyond end of input.")
         whole = max(1, 8 // (chunk * bps))              # samples in a byte of a thread's stream
-        if bin_samples % whole:
-            raise ValueError("state_series: bins are whole bytes: bin_samples must be a multiple of {} "
-                             "samples".format(whole))
-        if self.offset % whole:
-            raise ValueError("state_series: bins are whole bytes: seek to a multiple of {} samples".format(whole))
-        if count % whole:
-            raise ValueError("state_series: bins are whole bytes: count must be a multiple of {} "
-                             "samples".format(whole))
-        if not kernels.count_states_bins_supported(bps, chunk, bin_samples, nslot, payload):
-            raise NotImplementedError("state_series: the binned counting kernel does not take bins of {} samples "
-                                      "of {} codes x {} bits".format(bin_samples, chunk, bps))
-        kernels.require_gpu()
-        nbins = -(-count // bin_samples)
-        counts = torch.zeros((nslot, nbins, chunk, 1 << bps), dtype=torch.int32, device='cuda')
-        shape = tuple(self._states_shape(torch.empty((nslot, chunk, 1 << bps), device='meta')).shape)
 
-        def series():
-            return counts.permute(1, 0, 2, 3).reshape((nbins,) + shape)
+        def answer():
+            samples_left = self.shape[0] - self.offset
+            n = max(0, samples_left) if count is None or count < 0 else count
+            if n > samples_left:
+                raise EOFError("cannot read from beyond end of input.")
+            if bin_samples % whole:
+                raise ValueError("state_series: bins are whole bytes: bin_samples must be a multiple of {} "
+                                 "samples".format(whole))
+            if self.offset % whole:
+                raise ValueError("state_series: bins are whole bytes: seek to a multiple of {} samples".format(whole))
+            if n % whole:
+                raise ValueError("state_series: bins are whole bytes: count must be a multiple of {} "
+                                 "samples".format(whole))
+            if not kernels.count_states_bins_supported(bps, chunk, bin_samples, nslot, payload):
+                raise NotImplementedError("state_series: the binned counting kernel does not take bins of {} samples "
+                                          "of {} codes x {} bits".format(bin_samples, chunk, bps))
+            kernels.require_gpu()
+            nbins = -(-n // bin_samples)
+            counts = torch.zeros((nslot, nbins, chunk, 1 << bps), dtype=torch.int32, device='cuda')
+            shape = tuple(self._states_shape(torch.empty((nslot, chunk, 1 << bps), device='meta')).shape)
+            if n == 0:
+                return counts.permute(1, 0, 2, 3).reshape((nbins,) + shape), 0
+            spf = self.samples_per_frame
+            start, stop = self.offset, self.offset + n
 
-        if count == 0:
-            return series()
-        spf = self.samples_per_frame
-        start, stop = self.offset, self.offset + count
-        first, last = start // spf, -(-stop // spf)
-        set_nbytes = self._set_nbytes
+            def add(dbuf, src, s, e):
+                lo = max(start, s * spf)
+                kernels.count_states_bins(dbuf, e - s, payload, bps, chunk, nslot, bin_samples, nbins, src=src,
+                                          row_lo=lo - s * spf, row_hi=min(stop, e * spf) - s * spf,
+                                          first_row=lo - start, counts=counts)
 
-        def add(dbuf, src, s, e):
-            lo = max(start, s * spf)
-            kernels.count_states_bins(dbuf, e - s, payload, bps, chunk, nslot, bin_samples, nbins, src=src,
-                                      row_lo=lo - s * spf, row_hi=min(stop, e * spf) - s * spf,
-                                      first_row=lo - start, counts=counts)
+            nbad = self._walk_packed(start // spf, -(-stop // spf), add)
+            # (the permuted view of `counts`, or the copy a reshape of it had to make: taken after the walk)
+            return counts.permute(1, 0, 2, 3).reshape((nbins,) + shape), nbad
 
-        located = getattr(self, '_resident', None)
-        resident = self._resident_bytes()
-        if located is not None:
-            # a re-located index (bytes went missing): offsets into the whole file in HBM
-            dev, src = located
-            add(dev, src[first * nslot:last * nslot].contiguous(), first, last)
-        elif resident is not None:
-            lo = min(self._file_offset0 + first * set_nbytes, resident.numel())
-            hi = max(lo, min(self._file_offset0 + last * set_nbytes, resident.numel()))
-            win = self._device_window(resident, lo, hi)
-            add(win, self._states_index(win, first, last - first), first, last)
-        else:
-            image = self._image()
-            per_win = min(last - first, max(1, self.window_bytes // set_nbytes))
-            pipe = WindowPipeline(image, per_win * set_nbytes)
-            ranges, spans = [], []
-            for s in range(first, last, per_win):
-                e = min(last, s + per_win)
-                lo = min(self._file_offset0 + s * set_nbytes, len(image))
-                ranges.append((lo, max(lo, min(self._file_offset0 + e * set_nbytes, len(image)))))
-                spans.append((s, e))
-
-            def process(dbuf, i):
-                s, e = spans[i]
-                win = self._device_window(dbuf, 0, dbuf.numel())
-                add(win, self._states_index(win, s, e - s), s, e)
-
-            pipe.run(ranges, process)
-            pipe.release()
-        return series()
+        return self._answer_packed(answer)
 
     def power_series(self, bin_samples, count=None):
         """Mean ``|x|**2`` per valid sample and time bin, from `state_series`: float64
         device tensor of shape ``(nbins, nthread, nchan)`` (Mark 5B: ``(nbins, nchan)``),
         NaN where a bin holds no valid sample.  Exact up to float64 rounding: the power of
-        a bin is ``sum(counts * levels**2)``; nothing is decoded."""
+        a bin is ``sum(counts * levels**2)``; nothing is decoded.  Damaged files and
+        ``verify=True`` readers: as `state_series`."""
         counts = self.state_series(bin_samples, count)
         levels = torch.from_numpy(self.state_levels).to(counts.device).double()
         power = (counts.double() * levels ** 2).sum(-1)
@@ -1195,51 +1162,120 @@ class GPUStreamReaderBase:
             power, valid = power.sum(-1), valid[..., 0]
         return power / valid.double()
 
-    # -- format conversion on the packed bytes (kernels.repack_frames; baseband_amd.convert)
-    def _walk_packed(self, first, last, visit):
+    # -- the walk over the packed bytes that the statistics and the packed reads share
+    #    (kernels.count_states, count_states_bins, repack_frames; baseband_amd.convert)
+    def _walk_packed(self, first, last, visit, strict=False):
         """``visit(dbuf, src, s, e)`` for the frame sets [first, last) in pieces [s, e): the
         packed bytes of a piece on the device and its index of payload offsets into them
-        (-1: missing or invalid).  The three ways `state_counts` gets at the bytes: a
-        re-located index, resident bytes, or a `WindowPipeline` over the file image with
-        the un-fused scan and index."""
+        (-1: missing or invalid).  Three ways to the bytes: a re-located index, resident
+        bytes, or a `WindowPipeline` over the file image, the latter two with the un-fused
+        scan and index at the fixed stride.
+
+        Returns the number of frames that a verifying reader found missing or out of place
+        at the fixed stride -- the verdict ``read()`` gets from `_resolve_checks`, from the
+        same records (with the header behind the request where the format's read looks at
+        it) -- always 0 through a re-located index and under ``verify=False``.  What was
+        visited is then not the answer: `_answer_packed`.  `strict`: the walk stands in
+        for a read, so that a ``verify=True`` reader on a re-located index answers for the
+        sets it covers (`_strict_check`)."""
         nslot = self._states_geometry()[3]
         set_nbytes = self._set_nbytes
         located = getattr(self, '_resident', None)
-        resident = self._resident_bytes()
         if located is not None:
+            if strict and self.verify is True:
+                self._strict_check(first, last)
             dev, src = located
             visit(dev, src[first * nslot:last * nslot].contiguous(), first, last)
-        elif resident is not None:
+            return 0
+        verdict = _WalkVerdict() if self.verify else None
+        look = 1 if verdict is not None else 0
+        resident = self._resident_bytes()
+        if resident is not None:
             lo = min(self._file_offset0 + first * set_nbytes, resident.numel())
-            hi = max(lo, min(self._file_offset0 + last * set_nbytes, resident.numel()))
+            hi = max(lo, min(self._file_offset0 + (last + look) * set_nbytes, resident.numel()))
             win = self._device_window(resident, lo, hi)
-            visit(win, self._states_index(win, first, last - first), first, last)
+            visit(win, self._states_index(win, first, last - first, verdict), first, last)
         else:
             image = self._image()
             per_win = min(last - first, max(1, self.window_bytes // set_nbytes))
-            pipe = WindowPipeline(image, per_win * set_nbytes)
+            pipe = WindowPipeline(image, (per_win + look) * set_nbytes)
             ranges, spans = [], []
             for s in range(first, last, per_win):
                 e = min(last, s + per_win)
                 lo = min(self._file_offset0 + s * set_nbytes, len(image))
-                ranges.append((lo, max(lo, min(self._file_offset0 + e * set_nbytes, len(image)))))
+                ahead = look if e == last else 0        # (the header behind the request travels with its last window)
+                ranges.append((lo, max(lo, min(self._file_offset0 + (e + ahead) * set_nbytes, len(image)))))
                 spans.append((s, e))
 
             def process(dbuf, i):
                 s, e = spans[i]
                 win = self._device_window(dbuf, 0, dbuf.numel())
-                visit(win, self._states_index(win, s, e - s), s, e)
+                visit(win, self._states_index(win, s, e - s, verdict), s, e)
 
-            pipe.run(ranges, process)
-            pipe.release()
+            try:
+                pipe.run(ranges, process)
+            finally:
+                pipe.release()
+        return 0 if verdict is None else verdict.nbad()
+
+    def _strict_check(self, first, last):
+        """Raise what a ``verify=True`` read of the frame sets [first, last) through the
+        index of located frames raises (formats whose strict reads answer per set)."""
+
+    # what `_relocate` leaves on a reader
+    _relocation_state = ('_resident', '_nsample_found', '_located', '_relocated', '_damage', '_slips',
+                         '_before_trouble')
+    _lenient = None         # ... on a verify=True reader, for its statistics alone
+
+    def _relocated_meanwhile(self, answer):
+        """``answer()`` of a ``verify=True`` reader as its ``verify='fix'`` twin gives it:
+        through the index of located frames, which is made once and kept aside.  The
+        reader itself is left as it was -- its reads go on raising at what they meet."""
+        names = self._relocation_state
+        before = {k: self.__dict__[k] for k in names if k in self.__dict__}
+        try:
+            if self._lenient is None:
+                self._relocate()
+                self._lenient = {k: self.__dict__[k] for k in names if k in self.__dict__}
+            else:
+                self.__dict__.update(self._lenient)
+            return answer()
+        finally:
+            for k in names:
+                self.__dict__.pop(k, None)
+            self.__dict__.update(before)
+
+    def _answer_packed(self, answer, strict=False):
+        """What a method that works on the packed bytes returns.  ``answer()`` does all of
+        it for the reader as it stands -- takes `count`, checks it against the length,
+        makes the outputs, walks -- and returns ``(result, nbad)`` with `_walk_packed`'s
+        verdict.  When frames were missing or off the fixed stride the reader does what
+        ``read()`` does at that point: a ``verify='fix'`` reader locates its frames
+        (`_relocate`) and the WHOLE request is answered again through that index, with
+        the length the index gives; a ``verify=True`` reader raises the error of its read
+        when the method stands in for one (`strict`: `read_packed`, `frames_valid`), and
+        answers the statistics as its lenient twin would (`_relocated_meanwhile`)."""
+        result, nbad = answer()
+        if not nbad:
+            return result
+        if strict and self.verify is True:
+            msg = ("problem loading frame: {} frame header(s) failed verification "
+                   "(bad sync/invariants or unexpected time index)".format(nbad))
+            err = self._verification_error(msg)
+            if err is not None or not self._can_relocate:
+                raise err if err is not None else ValueError("wrong frame number. " + msg)
+        if not self._can_relocate or self._relocated:
+            return result
+        if self.verify is True and not strict:
+            return self._relocated_meanwhile(lambda: answer()[0])
+        self._relocate()
+        self.decode_ahead = False           # (as in read(): warnings belong to the read that meets a hole)
+        return answer()[0]
 
     def _packed_request(self, count):
-        if self.closed:
-            raise ValueError("I/O operation on closed stream.")
-        if self._states_geometry() is None:
-            raise NotImplementedError("{} has no packed reads".format(type(self).__name__))
         if count < 0 or count > self.shape[0] - self.offset:
             raise EOFError("cannot read from beyond end of input.")
+        self._asked = (self.offset, count)
 
     def _mark_invalid(self, marks, src, s, e, start, stop, spf_out):
         """Add to `marks` (int32 device tensor, one more entry than output frames: a
@@ -1257,8 +1293,14 @@ class GPUStreamReaderBase:
     def frames_valid(self, count, samples_per_frame):
         """Host bool array, one entry per frame of `samples_per_frame` samples that the
         next `count` samples from the current offset make up (the last one may be short):
-        true when every frame-slot of this stream the frame draws from is there and valid.
-        From the headers alone (scan and index); nothing is decoded, the offset stays."""
+        true when every frame-slot of this stream the frame draws from is there and valid,
+        that is, when ``read(count)`` would fill none of its samples.  From the headers
+        alone (scan and index); nothing is decoded, the offset stays.
+
+        The call stands in for the read: where ``read(count)`` under ``verify='fix'``
+        would locate the frames of a damaged file, so does this (and the answer is that
+        of the read which follows); where it would raise under ``verify=True``, this
+        raises the same."""
         if self.closed:
             raise ValueError("I/O operation on closed stream.")
         if count < 0 or count > self.shape[0] - self.offset:
@@ -1266,13 +1308,20 @@ class GPUStreamReaderBase:
         nout = -(-count // samples_per_frame)
         if self._states_geometry() is None or count == 0:   # (no index of payloads: nothing known to be missing)
             return np.ones(nout, bool)
-        kernels.require_gpu()
-        spf = self.samples_per_frame
-        start, stop = self.offset, self.offset + count
-        marks = torch.zeros(nout + 1, dtype=torch.int32, device='cuda')
-        self._walk_packed(start // spf, -(-stop // spf),
-                          lambda dbuf, src, s, e: self._mark_invalid(marks, src, s, e, start, stop, samples_per_frame))
-        return (torch.cumsum(marks, 0)[:nout] == 0).cpu().numpy()
+
+        def answer():
+            self._packed_request(count)
+            kernels.require_gpu()
+            spf = self.samples_per_frame
+            start, stop = self.offset, self.offset + count
+            marks = torch.zeros(nout + 1, dtype=torch.int32, device='cuda')
+            nbad = self._walk_packed(
+                start // spf, -(-stop // spf),
+                lambda dbuf, src, s, e: self._mark_invalid(marks, src, s, e, start, stop, samples_per_frame),
+                strict=True)
+            return (torch.cumsum(marks, 0)[:nout] == 0).cpu().numpy(), nbad
+
+        return self._answer_packed(answer, strict=True)
 
     def read_packed(self, count, coder, nthread, nchan, samples_per_frame, fill_code):
         """The next `count` samples as packed payloads of another frame geometry, without
@@ -1284,8 +1333,17 @@ class GPUStreamReaderBase:
         output frame draws from is there and valid.  Samples of the others hold
         `fill_code`.  `count` is a whole number of output frames; the offset must lie on a
         byte boundary of a thread's stream on both sides.  Threads follow the reader's
-        selection; a channel `subset` is not applied.  Advances the offset."""
+        selection; a channel `subset` is not applied.  Advances the offset.
+
+        A read in every respect but the decoding: a damaged file is repaired under
+        ``verify='fix'`` as ``read(count)`` repairs it (the frames are located and the
+        whole request is answered through that index), and ``verify=True`` raises what
+        ``read(count)`` raises; the offset then stays."""
         count = operator.index(count)
+        if self.closed:
+            raise ValueError("I/O operation on closed stream.")
+        if self._states_geometry() is None:
+            raise NotImplementedError("{} has no packed reads".format(type(self).__name__))
         self._packed_request(count)
         coder_in, bps, chunk_in, nslot_in, payload_in = self._states_geometry()
         chunk_out = nchan * (2 if self.complex_data else 1)
@@ -1305,22 +1363,27 @@ class GPUStreamReaderBase:
             raise ValueError("read_packed: whole bytes only: seek to a multiple of {} samples".format(whole))
         kernels.require_gpu()
         nout = count // samples_per_frame
-        out = torch.empty((nout, nthread, payload_out), dtype=torch.uint8, device='cuda')
         if count == 0:
-            return out, np.ones(0, bool)
-        spf = self.samples_per_frame
-        start, stop = self.offset, self.offset + count
-        marks = torch.zeros(nout + 1, dtype=torch.int32, device='cuda')
+            return torch.empty((0, nthread, payload_out), dtype=torch.uint8, device='cuda'), np.ones(0, bool)
 
-        def visit(dbuf, src, s, e):
-            lo = max(start, s * spf)
-            kernels.repack_frames(dbuf, e - s, payload_in, bps, coder_in, chunk_in, nslot_in, coder, chunk_out,
-                                  nthread, payload_out, fill_code=fill_code, src=src, row_lo=lo - s * spf,
-                                  row_hi=min(stop, e * spf) - s * spf, first_row=lo - start, out=out.reshape(-1))
-            self._mark_invalid(marks, src, s, e, start, stop, samples_per_frame)
+        def answer():
+            self._packed_request(count)
+            out = torch.empty((nout, nthread, payload_out), dtype=torch.uint8, device='cuda')
+            spf = self.samples_per_frame
+            start, stop = self.offset, self.offset + count
+            marks = torch.zeros(nout + 1, dtype=torch.int32, device='cuda')
 
-        self._walk_packed(start // spf, -(-stop // spf), visit)
-        valid = (torch.cumsum(marks, 0)[:nout] == 0).cpu().numpy()
+            def visit(dbuf, src, s, e):
+                lo = max(start, s * spf)
+                kernels.repack_frames(dbuf, e - s, payload_in, bps, coder_in, chunk_in, nslot_in, coder, chunk_out,
+                                      nthread, payload_out, fill_code=fill_code, src=src, row_lo=lo - s * spf,
+                                      row_hi=min(stop, e * spf) - s * spf, first_row=lo - start, out=out.reshape(-1))
+                self._mark_invalid(marks, src, s, e, start, stop, samples_per_frame)
+
+            nbad = self._walk_packed(start // spf, -(-stop // spf), visit, strict=True)
+            return (out, (torch.cumsum(marks, 0)[:nout] == 0).cpu().numpy()), nbad
+
+        out, valid = self._answer_packed(answer, strict=True)
         self.offset += count
         return out, valid
 

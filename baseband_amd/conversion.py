@@ -81,16 +81,48 @@ def _packed_plan(fr, fw):
     return None, (coder_out, nthread, nchan, spf, fill)
 
 
-def _convert_loop(fr, fw, count):
+class _Request:
+    """The samples a `convert` call still owes: `count` of them from where the reader stood,
+    or -- `count` None or negative -- all that the reader holds.  The reader's length is
+    asked for again at every piece: a ``verify='fix'`` reader that meets damage locates its
+    frames then, and the length is from there on what that index says."""
+
+    def __init__(self, fr, count):
+        self.fr, self.start = fr, fr.offset
+        self.count = None if count is None or count < 0 else count
+        if self.left() < 0:
+            raise EOFError("cannot read from beyond end of input.")
+
+    def left(self):
+        total = self.fr.shape[0] - self.start if self.count is None else self.count
+        return total - (self.fr.offset - self.start)
+
+    def piece(self, most, call, unit=1):
+        """``call(n)`` for the next ``n <= most`` samples (whole `unit`s) -> (n, what it returned).
+        When the call itself made the reader locate its frames and an open-ended request ends
+        earlier for it, the piece is asked for again at its new size (once: frames are located
+        once)."""
+        n = min(most, self.left()) // unit * unit
+        length = self.fr.shape[0]
+        try:
+            return n, call(n)
+        except EOFError:
+            if self.count is not None or self.fr.shape[0] == length:
+                raise
+        n = min(most, self.left()) // unit * unit
+        return n, call(n)
+
+
+def _convert_loop(fr, fw, request):
     """``fw.write(fr.read(spf), valid=v)`` frame after frame, in pieces of many frames:
-    runs of frames of equal validity are written with one call."""
+    runs of frames of equal validity are written with one call.  `fr.frames_valid` stands
+    in for the read that follows it -- it repairs or raises where that read would -- so its
+    answer is about the samples that read returns."""
     spf = fw.samples_per_frame
     ncomp = int(np.prod(fw._unsliced_shape)) * (2 if fw.complex_data else 1)
     per = max(1, LOOP_PIECE_BYTES // (4 * spf * ncomp))
-    done = 0
-    while done < count:
-        n = min(per * spf, count - done)
-        valid = fr.frames_valid(n, spf)
+    while request.left() > 0:
+        n, valid = request.piece(per * spf, lambda n: fr.frames_valid(n, spf))
         data = fr.read(n)
         data = data.reshape((data.shape[0],) + fw.sample_shape)
         k = 0
@@ -100,7 +132,6 @@ def _convert_loop(fr, fw, count):
                 e += 1
             fw.write(data[k * spf:e * spf], valid=bool(valid[k]))
             k = e
-        done += n
 
 
 def convert(fr, fw, count=None, packed=None):
@@ -120,29 +151,27 @@ def convert(fr, fw, count=None, packed=None):
     GPU (`kernels.repack_frames`) in pieces of at most 256 MiB.  ``packed=None`` takes that
     path when it applies, ``packed=False`` never, ``packed=True`` raises
     NotImplementedError naming the reason when it does not.  Mark 4, DADA, GUPPI and GSB
-    streams, and conversions that rescale, go through the loop."""
-    samples_left = fr.shape[0] - fr.offset
-    if count is None or count < 0:
-        count = max(0, samples_left)
-    if count > samples_left:
-        raise EOFError("cannot read from beyond end of input.")
+    streams, and conversions that rescale, go through the loop.
+
+    A damaged file is converted as ``read()`` reads it on either path: under
+    ``verify='fix'`` the piece that meets the damage has the frames located and is
+    answered, samples and validity alike, through that index; under ``verify=True`` it
+    raises what the read raises.  Without `count` the request ends where the reader ends
+    once its frames are located."""
+    request = _Request(fr, count)
     kernels.require_gpu()
     reason, plan = (None, None) if packed is False else _packed_plan(fr, fw)
     if packed and reason is not None:
         raise NotImplementedError("convert(packed=True): " + reason)
-    if packed is False or reason is not None:
-        _convert_loop(fr, fw, count)
-        return count
-    coder, nthread, nchan, spf, fill = plan
-    payload = spf * nchan * (2 if fw.complex_data else 1) * fw.bps // 8
-    per = max(1, PACKED_PIECE_BYTES // (nthread * payload))
-    nfull = count // spf
-    for k in range(0, nfull, per):
-        n = min(per, nfull - k)
-        payloads, valid = fr.read_packed(n * spf, coder, nthread, nchan, spf, fill)
-        fw._write_packed(payloads, valid)
-        fw._nframes_written += n
-        fw.offset += n * spf
-    if count - nfull * spf:
-        _convert_loop(fr, fw, count - nfull * spf)
-    return count
+    if packed is not False and reason is None:
+        coder, nthread, nchan, spf, fill = plan
+        payload = spf * nchan * (2 if fw.complex_data else 1) * fw.bps // 8
+        per = max(1, PACKED_PIECE_BYTES // (nthread * payload))
+        while request.left() >= spf:
+            n, (payloads, valid) = request.piece(
+                per * spf, lambda n: fr.read_packed(n, coder, nthread, nchan, spf, fill), unit=spf)
+            fw._write_packed(payloads, valid)
+            fw._nframes_written += n // spf
+            fw.offset += n
+    _convert_loop(fr, fw, request)              # (everything, or a tail of less than a frame)
+    return fr.offset - request.start

@@ -224,12 +224,19 @@ class Mark5BStreamReader(GPUStreamReaderBase):
     def _states_geometry(self):
         return (_lib.CODER_MARK5B, self.bps, self._unsliced_shape[0], 1, 10000)
 
-    def _states_index(self, dbuf, first, nsets):
-        nframes = min(nsets, dbuf.numel() // FRAME_NBYTES)
+    def _states_index(self, dbuf, first, nsets, verdict=None):
+        """`verdict` (base._WalkVerdict): the records are verified as `_process_window` has them
+        verified -- every frame in place, the header behind the last one a header when `dbuf`
+        holds it, frames the bytes do not reach counted as missing."""
+        nframes = min(nsets + (1 if verdict is not None else 0), dbuf.numel() // FRAME_NBYTES)
+        if verdict is not None:
+            verdict.missing += max(0, nsets - nframes)
         if nframes == 0:
             return torch.full((nsets,), -1, dtype=torch.int64, device=dbuf.device)
         recs = kernels.mark5b_scan(dbuf, nframes, self._ref_seconds, self.header0['frame_nr'] + first,
                                    self._frame_rate, by_position=not self.verify)
+        if verdict is not None:
+            kernels.verify_records(recs, nframes, 0, 1, min(nsets, nframes), verdict.counter)
         return kernels.build_index(recs, nsets, 1, None)
 
     def _states_shape(self, counts):

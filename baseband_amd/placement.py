@@ -80,7 +80,7 @@ def reader_closed():
 
 _idle_deadline = None            # time.monotonic() after which the watcher trims (None: nothing scheduled)
 _idle_watcher = None             # the daemon thread waiting for that deadline
-_idle_lock = threading.Lock()
+_idle_lock = threading.RLock()     # (re-entrant: a reader's `__del__` run by the garbage collector ends here too)
 
 
 _idle_trims = 0                  # idle trims that released memory so far (each doubles the next delay)

@@ -721,7 +721,11 @@ class _FileSink:
 
 
 _sinks = {}                 # id(file handle) -> _FileSink (which keeps the handle: `_FileSink.key`)
-_sinks_lock = threading.Lock()
+# Re-entrant: a handle that dies in a reference cycle (a writer kept alive by the traceback of an
+# exception, say) is finalized by the garbage collector, which runs wherever an allocation
+# triggers it -- also on a thread that is inside this lock making a `_FileSink` -- and
+# `_drop_sink` takes the lock again there.  With a plain lock that thread waited for itself.
+_sinks_lock = threading.RLock()
 _WRITE_ASYNC = os.environ.get('BB_WRITE_ASYNC', '1') not in ('0', 'no', 'off')
 
 

@@ -542,10 +542,7 @@ class VDIFStreamReader(GPUStreamReaderBase):
             return super()._decode_sets(first, last, into, elem)
         dev, src = self._resident
         if self.verify is True:         # (strict: every read answers for the sets it covers)
-            err = self._strict_error(self._first_problem_met(first, last),
-                                     "problem loading frame set in {}..{}".format(first, last - 1))
-            if err is not None:
-                raise err
+            self._strict_check(first, last)
         self._warn_damage(first, last)
         h0 = self.header0
         nslot = len(self._thread_ids)
@@ -559,6 +556,12 @@ class VDIFStreamReader(GPUStreamReaderBase):
         if self.complex_data:
             flat = torch.view_as_complex(flat.view(-1, 2))
         return flat.reshape((nsets * self.samples_per_frame,) + tuple(self._decode_shape))
+
+    def _strict_check(self, first, last):
+        err = self._strict_error(self._first_problem_met(first, last),
+                                 "problem loading frame set in {}..{}".format(first, last - 1))
+        if err is not None:
+            raise err
 
     def _get_index(self, header):
         """Frame-set index relative to header0 (vdif/base.py:386-390)."""
@@ -669,12 +672,16 @@ class VDIFStreamReader(GPUStreamReaderBase):
         return (self._coder, self.bps, h0.nchan * (2 if self.complex_data else 1), len(self._thread_ids),
                 h0.payload_nbytes)
 
-    def _states_index(self, dbuf, first, nsets):
-        """The un-fused scan and index of `build_index` for the frame sets `dbuf` starts with."""
+    def _states_index(self, dbuf, first, nsets, verdict=None):
+        """The un-fused scan and index of `build_index` for the frame sets `dbuf` starts with.
+        `verdict` (base._WalkVerdict): the records are verified as `_process_window` has them
+        verified -- every frame in place, frames the bytes do not reach counted as missing."""
         h0 = self.header0
         nslot = len(self._thread_ids)
         nthread_file = len(self._file_threads)
         nframes = min(nsets * nthread_file, dbuf.numel() // self._frame_nbytes)
+        if verdict is not None:
+            verdict.missing += nsets * nthread_file - nframes
         if nframes == 0:
             return torch.full((nsets * nslot,), -1, dtype=torch.int64, device=dbuf.device)
         if self._thread_slot is None:
@@ -682,6 +689,8 @@ class VDIFStreamReader(GPUStreamReaderBase):
         recs = kernels.vdif_scan(dbuf, nframes, self._frame_nbytes, h0.nbytes, self._pattern,
                                  self._mask if self.verify else [0] * len(self._mask), h0['seconds'],
                                  h0['frame_nr'] + first, self._frame_rate, set_nframes=nthread_file)
+        if verdict is not None:
+            kernels.verify_records(recs, nframes, 0, nthread_file, nframes, verdict.counter)
         return kernels.build_index(recs, nsets, nslot, self._thread_slot)
 
     def _states_shape(self, counts):

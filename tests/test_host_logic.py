@@ -1281,6 +1281,36 @@ def test_file_sink_belongs_to_one_handle(tmp_path):
     assert open(b, 'rb').read() == b'second+queued'
 
 
+def test_a_handle_finalized_inside_the_sink_registry_does_not_wait_for_itself(tmp_path):
+    """A handle that dies in a reference cycle is finalized by the garbage collector, on
+    whatever thread an allocation triggers it -- also one that holds the registry's lock while
+    it makes a sink.  `_drop_sink` takes that lock: the thread must get through."""
+    import gc
+    import threading
+    from baseband_amd import staging
+    from baseband_amd.base.base import FileBase
+    raw = open(str(tmp_path / 'cycle.bin'), 'wb')
+    fh = FileBase(raw)
+    sink = staging._sink_for(fh)
+    staging.write_host_bytes(fh, b'queued')
+    fh.__dict__['myself'] = fh                          # only the collector frees it now
+    del fh
+    done = []
+
+    def collect_inside_the_lock():
+        with staging._sinks_lock:
+            gc.collect()
+        done.append(True)
+
+    t = threading.Thread(target=collect_inside_the_lock, daemon=True)
+    t.start()
+    t.join(10)
+    assert done and not t.is_alive()
+    assert sink.closed and not any(s is sink for s in staging._sinks.values())
+    raw.close()
+    assert open(str(tmp_path / 'cycle.bin'), 'rb').read() == b'queued'
+
+
 def test_file_sink_positional_resyncs_after_side_writes(tmp_path):
     """A sequence writer's sink keeps its own stream offset; bytes written on the handle
     itself between queued pieces (after a drain) must not be overwritten by the next piece."""
