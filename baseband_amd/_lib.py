@@ -295,21 +295,25 @@ def get_levels(coder, bps):
     return out
 
 
+def states_params(bps, chunk=1, nslot=1, payload_nbytes=4, src0=0, src_stride=0, row_lo=0, row_hi=0, reserved=0):
+    p = StatesParams()
+    p.bps, p.chunk, p.nslot, p.reserved = bps, chunk, nslot, reserved
+    p.payload_nbytes, p.src0, p.src_stride = payload_nbytes, src0, src_stride
+    p.row_lo, p.row_hi = row_lo, row_hi
+    return p
+
+
 def count_states_check(bps, chunk=1, nslot=1, payload_nbytes=4, row_lo=0, row_hi=0, reserved=0):
     """What `bb_count_states` would answer to these parameters, as far as they decide it
     (bb_count_states_check: no buffers, no device): BB_OK, BB_EINVAL or BB_ENOTSUP."""
-    p = StatesParams()
-    p.bps, p.chunk, p.nslot, p.reserved = bps, chunk, nslot, reserved
-    p.payload_nbytes, p.row_lo, p.row_hi = payload_nbytes, row_lo, row_hi
+    p = states_params(bps, chunk, nslot, payload_nbytes, 0, 0, row_lo, row_hi, reserved)
     return lib.bb_count_states_check(C.byref(p))
 
 
 def count_states_bins_check(bps, chunk=1, bin_rows=8, nslot=1, payload_nbytes=4, row_lo=0, row_hi=0, reserved=0):
     """What `bb_count_states_bins` would answer to these parameters, as far as they decide
     it (bb_count_states_bins_check: no buffers, no device): BB_OK, BB_EINVAL or BB_ENOTSUP."""
-    p = StatesParams()
-    p.bps, p.chunk, p.nslot, p.reserved = bps, chunk, nslot, reserved
-    p.payload_nbytes, p.row_lo, p.row_hi = payload_nbytes, row_lo, row_hi
+    p = states_params(bps, chunk, nslot, payload_nbytes, 0, 0, row_lo, row_hi, reserved)
     return lib.bb_count_states_bins_check(C.byref(p), bin_rows)
 
 

@@ -25,6 +25,7 @@ from .. import kernels
 from ..placement import empty_output
 from .. import placement as _placement
 from ..staging import host_image, WindowPipeline
+from .packed import PackedBytesMixin
 from .quantities import as_time, as_timedelta, is_time_like, is_duration_like
 
 # BB_SIDE_SCAN=0: the scan of a request on resident bytes stays on the caller's stream
@@ -381,20 +382,6 @@ class _FileReaderInfoProperty:
 VLBIFileReaderBase.info = _FileReaderInfoProperty()
 
 
-class _WalkVerdict:
-    """What a walk over packed bytes at the fixed stride learns about its frames
-    (`GPUStreamReaderBase._walk_packed`): a device counter that bb_verify_records adds to,
-    and the frames the file's bytes did not reach (known on the host)."""
-    __slots__ = ('counter', 'missing')
-
-    def __init__(self):
-        self.counter = torch.zeros(1, dtype=torch.int32, device='cuda')
-        self.missing = 0
-
-    def nbad(self):
-        return self.missing + int(self.counter.item())
-
-
 def _to_host_array(data, out):
     """Device tensor -> the caller's NumPy `out`: pinned double-buffered copy
     for large contiguous destinations, plain copy otherwise."""
@@ -411,7 +398,7 @@ def _apply_squeeze(shape):
     return tuple(s for s in shape if s > 1)
 
 
-class GPUStreamReaderBase:
+class GPUStreamReaderBase(PackedBytesMixin):
     """Sample-stream view of a file whose frames decode on the GPU.
 
     Subclasses set up the geometry (`_setup`) and implement
@@ -1006,386 +993,9 @@ class GPUStreamReaderBase:
             _to_host_array(data, out)
         return out
 
-    # -- sampler statistics (kernels.count_states; readers whose frames are fixed-stride
-    #    payloads of LSB-first codes define `_states_geometry` and `_states_index`)
-    def _states_geometry(self):
-        """(coder, bps, chunk, nslot, payload_nbytes) of the packed samples, or None."""
-        return None
-
-    def _states_index(self, dbuf, first, nsets):
-        """Payload offsets into `dbuf`, which starts at frame set `first`, for `nsets`
-        frame sets (-1: missing or invalid): header scan and index, nothing else."""
-        raise NotImplementedError
-
-    def _states_shape(self, counts):
-        return counts
-
-    @property
-    def state_levels(self):
-        """float32 NumPy array of the ``2**bps`` levels of this stream's coder, by raw
-        code: with ``c = fh.state_counts()``, ``(c * levels**2).sum(-1) / c.sum(-1)`` is
-        the mean power."""
-        geom = self._states_geometry()
-        if geom is None:
-            raise NotImplementedError("{} has no sampler statistics".format(type(self).__name__))
-        return _lib.get_levels(geom[0], geom[1])
-
-    def state_counts(self, count=None):
-        """How often each raw sample code occurs among the samples ``read(count)``
-        would return from the current offset -> int64 device tensor whose last axis
-        counts codes ``0 .. 2**bps - 1`` (levels: `state_levels`).  Counted from the
-        packed bytes (bb_count_states): one pass over the file's bytes, nothing is
-        decoded and the offset does not move.  Samples of frames that ``read()`` would
-        fill (missing or invalid ones) are left out; bad frames do not raise.  Threads
-        follow the reader's selection; a channel `subset` is NOT applied: counting
-        every channel costs nothing more.
-
-        A file that lost bytes or frames is counted as ``read()`` under ``verify='fix'``
-        reads it, whatever has been read before: when the pass meets headers that are
-        missing or off the fixed stride, the frames are located byte by byte
-        (`_relocate`, as a read would) and the whole request is counted again through
-        that index.  A ``verify=True`` reader gives the same counts and stays strict:
-        the index is used for the statistics only.  ``verify=False`` counts what stands
-        at the fixed stride."""
-        if self.closed:
-            raise ValueError("I/O operation on closed stream.")
-        geom = self._states_geometry()
-        if geom is None:
-            raise NotImplementedError("{} has no sampler statistics".format(type(self).__name__))
-        _, bps, chunk, nslot, payload = geom
-        if not kernels.count_states_supported(bps, chunk, nslot, payload):
-            raise NotImplementedError(
-                "state_counts: a complete sample of {} codes x {} bits is not one the counting kernel "
-                "takes (a power of two of codes, chunk * bps <= {})".format(chunk, bps, kernels.STATES_MAX_ROW_BITS))
-
-        def answer():
-            samples_left = self.shape[0] - self.offset
-            n = max(0, samples_left) if count is None or count < 0 else count
-            if n > samples_left:
-                raise EOFError("cannot read from beyond end of input.")
-            kernels.require_gpu()
-            counts = torch.zeros((nslot, chunk, 1 << bps), dtype=torch.int64, device='cuda')
-            if n == 0:
-                return self._states_shape(counts), 0
-            spf = self.samples_per_frame
-            start, stop = self.offset, self.offset + n
-
-            def add(dbuf, src, s, e):
-                kernels.count_states(dbuf, e - s, payload, bps, chunk, nslot, src=src,
-                                     row_lo=max(start, s * spf) - s * spf, row_hi=min(stop, e * spf) - s * spf,
-                                     counts=counts)
-
-            nbad = self._walk_packed(start // spf, -(-stop // spf), add)
-            return self._states_shape(counts), nbad
-
-        return self._answer_packed(answer)
-
-    def state_series(self, bin_samples, count=None):
-        """`state_counts` as a time series: int32 device tensor of shape ``(nbins,) +
-        state_counts().shape`` with ``nbins = ceil(count / bin_samples)``; bin ``b`` counts
-        the samples ``[offset + b * bin_samples, offset + (b + 1) * bin_samples)`` of what
-        ``read(count)`` would return (the last bin may be short).  Counted from the packed
-        bytes (bb_count_states_bins): one pass, nothing is decoded, the offset does not
-        move.  Samples of missing or invalid frames are left out, so a bin's sum over the
-        code axis is its number of valid samples, and ``state_series(n, count).sum(0)``
-        equals ``state_counts(count)``.  Bins are whole bytes of a thread's stream:
-        `bin_samples`, the offset and `count` must be multiples of ``8 / (codes per sample
-        * bps)`` samples where that is more than one.  Damaged files and ``verify=True``
-        readers: as `state_counts` -- the frames are located, bad frames do not raise."""
-        if self.closed:
-            raise ValueError("I/O operation on closed stream.")
-        geom = self._states_geometry()
-        if geom is None:
-            raise NotImplementedError("{} has no sampler statistics".format(type(self).__name__))
-        _, bps, chunk, nslot, payload = geom
-        bin_samples = operator.index(bin_samples)
-        if bin_samples < 1:
-            raise ValueError("state_series: bin_samples must be at least 1")
-        if bin_samples > 0x7fffffff:
-            raise ValueError("state_series: bin_samples must be below 2**31")
-        if not kernels.count_states_supported(bps, chunk, nslot, payload) or \
-                chunk << bps > kernels.STATES_BINS_MAX_COUNTERS:
-            raise NotImplementedError(
-                "state_series: a complete sample of {} codes x {} bits is not one the binned counting kernel "
-                "takes (a power of two of codes, chunk * bps <= {}, chunk << bps <= {})".format(
-                    chunk, bps, kernels.STATES_MAX_ROW_BITS, kernels.STATES_BINS_MAX_COUNTERS))
-        whole = max(1, 8 // (chunk * bps))              # samples in a byte of a thread's stream
-
-        def answer():
-            samples_left = self.shape[0] - self.offset
-            n = max(0, samples_left) if count is None or count < 0 else count
-            if n > samples_left:
-                raise EOFError("cannot read from beyond end of input.")
-            if bin_samples % whole:
-                raise ValueError("state_series: bins are whole bytes: bin_samples must be a multiple of {} "
-                                 "samples".format(whole))
-            if self.offset % whole:
-                raise ValueError("state_series: bins are whole bytes: seek to a multiple of {} samples".format(whole))
-            if n % whole:
-                raise ValueError("state_series: bins are whole bytes: count must be a multiple of {} "
-                                 "samples".format(whole))
-            if not kernels.count_states_bins_supported(bps, chunk, bin_samples, nslot, payload):
-                raise NotImplementedError("state_series: the binned counting kernel does not take bins of {} samples "
-                                          "of {} codes x {} bits".format(bin_samples, chunk, bps))
-            kernels.require_gpu()
-            nbins = -(-n // bin_samples)
-            counts = torch.zeros((nslot, nbins, chunk, 1 << bps), dtype=torch.int32, device='cuda')
-            shape = tuple(self._states_shape(torch.empty((nslot, chunk, 1 << bps), device='meta')).shape)
-            if n == 0:
-                return counts.permute(1, 0, 2, 3).reshape((nbins,) + shape), 0
-            spf = self.samples_per_frame
-            start, stop = self.offset, self.offset + n
-
-            def add(dbuf, src, s, e):
-                lo = max(start, s * spf)
-                kernels.count_states_bins(dbuf, e - s, payload, bps, chunk, nslot, bin_samples, nbins, src=src,
-                                          row_lo=lo - s * spf, row_hi=min(stop, e * spf) - s * spf,
-                                          first_row=lo - start, counts=counts)
-
-            nbad = self._walk_packed(start // spf, -(-stop // spf), add)
-            # (the permuted view of `counts`, or the copy a reshape of it had to make: taken after the walk)
-            return counts.permute(1, 0, 2, 3).reshape((nbins,) + shape), nbad
-
-        return self._answer_packed(answer)
-
-    def power_series(self, bin_samples, count=None):
-        """Mean ``|x|**2`` per valid sample and time bin, from `state_series`: float64
-        device tensor of shape ``(nbins, nthread, nchan)`` (Mark 5B: ``(nbins, nchan)``),
-        NaN where a bin holds no valid sample.  Exact up to float64 rounding: the power of
-        a bin is ``sum(counts * levels**2)``; nothing is decoded.  Damaged files and
-        ``verify=True`` readers: as `state_series`."""
-        counts = self.state_series(bin_samples, count)
-        levels = torch.from_numpy(self.state_levels).to(counts.device).double()
-        power = (counts.double() * levels ** 2).sum(-1)
-        valid = counts.sum(-1, dtype=torch.int64)
-        if self.complex_data:                           # (re, im) axis: a sample has both
-            power, valid = power.sum(-1), valid[..., 0]
-        return power / valid.double()
-
-    # -- the walk over the packed bytes that the statistics and the packed reads share
-    #    (kernels.count_states, count_states_bins, repack_frames; baseband_amd.convert)
-    def _walk_packed(self, first, last, visit, strict=False):
-        """``visit(dbuf, src, s, e)`` for the frame sets [first, last) in pieces [s, e): the
-        packed bytes of a piece on the device and its index of payload offsets into them
-        (-1: missing or invalid).  Three ways to the bytes: a re-located index, resident
-        bytes, or a `WindowPipeline` over the file image, the latter two with the un-fused
-        scan and index at the fixed stride.
-
-        Returns the number of frames that a verifying reader found missing or out of place
-        at the fixed stride -- the verdict ``read()`` gets from `_resolve_checks`, from the
-        same records (with the header behind the request where the format's read looks at
-        it) -- always 0 through a re-located index and under ``verify=False``.  What was
-        visited is then not the answer: `_answer_packed`.  `strict`: the walk stands in
-        for a read, so that a ``verify=True`` reader on a re-located index answers for the
-        sets it covers (`_strict_check`)."""
-        nslot = self._states_geometry()[3]
-        set_nbytes = self._set_nbytes
-        located = getattr(self, '_resident', None)
-        if located is not None:
-            if strict and self.verify is True:
-                self._strict_check(first, last)
-            dev, src = located
-            visit(dev, src[first * nslot:last * nslot].contiguous(), first, last)
-            return 0
-        verdict = _WalkVerdict() if self.verify else None
-        look = 1 if verdict is not None else 0
-        resident = self._resident_bytes()
-        if resident is not None:
-            lo = min(self._file_offset0 + first * set_nbytes, resident.numel())
-            hi = max(lo, min(self._file_offset0 + (last + look) * set_nbytes, resident.numel()))
-            win = self._device_window(resident, lo, hi)
-            visit(win, self._states_index(win, first, last - first, verdict), first, last)
-        else:
-            image = self._image()
-            per_win = min(last - first, max(1, self.window_bytes // set_nbytes))
-            pipe = WindowPipeline(image, (per_win + look) * set_nbytes)
-            ranges, spans = [], []
-            for s in range(first, last, per_win):
-                e = min(last, s + per_win)
-                lo = min(self._file_offset0 + s * set_nbytes, len(image))
-                ahead = look if e == last else 0        # (the header behind the request travels with its last window)
-                ranges.append((lo, max(lo, min(self._file_offset0 + (e + ahead) * set_nbytes, len(image)))))
-                spans.append((s, e))
-
-            def process(dbuf, i):
-                s, e = spans[i]
-                win = self._device_window(dbuf, 0, dbuf.numel())
-                visit(win, self._states_index(win, s, e - s, verdict), s, e)
-
-            try:
-                pipe.run(ranges, process)
-            finally:
-                pipe.release()
-        return 0 if verdict is None else verdict.nbad()
-
-    def _strict_check(self, first, last):
-        """Raise what a ``verify=True`` read of the frame sets [first, last) through the
-        index of located frames raises (formats whose strict reads answer per set)."""
-
-    # what `_relocate` leaves on a reader
+    # what `_relocate` leaves on a reader (`packed._relocated_meanwhile` sets it aside and puts it back)
     _relocation_state = ('_resident', '_nsample_found', '_located', '_relocated', '_damage', '_slips',
                          '_before_trouble')
-    _lenient = None         # ... on a verify=True reader, for its statistics alone
-
-    def _relocated_meanwhile(self, answer):
-        """``answer()`` of a ``verify=True`` reader as its ``verify='fix'`` twin gives it:
-        through the index of located frames, which is made once and kept aside.  The
-        reader itself is left as it was -- its reads go on raising at what they meet."""
-        names = self._relocation_state
-        before = {k: self.__dict__[k] for k in names if k in self.__dict__}
-        try:
-            if self._lenient is None:
-                self._relocate()
-                self._lenient = {k: self.__dict__[k] for k in names if k in self.__dict__}
-            else:
-                self.__dict__.update(self._lenient)
-            return answer()
-        finally:
-            for k in names:
-                self.__dict__.pop(k, None)
-            self.__dict__.update(before)
-
-    def _answer_packed(self, answer, strict=False):
-        """What a method that works on the packed bytes returns.  ``answer()`` does all of
-        it for the reader as it stands -- takes `count`, checks it against the length,
-        makes the outputs, walks -- and returns ``(result, nbad)`` with `_walk_packed`'s
-        verdict.  When frames were missing or off the fixed stride the reader does what
-        ``read()`` does at that point: a ``verify='fix'`` reader locates its frames
-        (`_relocate`) and the WHOLE request is answered again through that index, with
-        the length the index gives; a ``verify=True`` reader raises the error of its read
-        when the method stands in for one (`strict`: `read_packed`, `frames_valid`), and
-        answers the statistics as its lenient twin would (`_relocated_meanwhile`)."""
-        result, nbad = answer()
-        if not nbad:
-            return result
-        if strict and self.verify is True:
-            msg = ("problem loading frame: {} frame header(s) failed verification "
-                   "(bad sync/invariants or unexpected time index)".format(nbad))
-            err = self._verification_error(msg)
-            if err is not None or not self._can_relocate:
-                raise err if err is not None else ValueError("wrong frame number. " + msg)
-        if not self._can_relocate or self._relocated:
-            return result
-        if self.verify is True and not strict:
-            return self._relocated_meanwhile(lambda: answer()[0])
-        self._relocate()
-        self.decode_ahead = False           # (as in read(): warnings belong to the read that meets a hole)
-        return answer()[0]
-
-    def _packed_request(self, count):
-        if count < 0 or count > self.shape[0] - self.offset:
-            raise EOFError("cannot read from beyond end of input.")
-        self._asked = (self.offset, count)
-
-    def _mark_invalid(self, marks, src, s, e, start, stop, spf_out):
-        """Add to `marks` (int32 device tensor, one more entry than output frames: a
-        difference array) the output frames that draw from a frame set of [s, e) with an
-        index entry below 0."""
-        nslot = self._states_geometry()[3]
-        spf = self.samples_per_frame
-        bad = torch.nonzero((src.reshape(e - s, nslot) < 0).any(1)).reshape(-1) + s
-        lo = torch.clamp(bad * spf, min=start) - start
-        hi = torch.clamp((bad + 1) * spf, max=stop) - 1 - start
-        one = torch.ones_like(bad, dtype=torch.int32)
-        marks.index_add_(0, torch.div(lo, spf_out, rounding_mode='floor'), one)
-        marks.index_add_(0, torch.div(hi, spf_out, rounding_mode='floor') + 1, -one)
-
-    def frames_valid(self, count, samples_per_frame):
-        """Host bool array, one entry per frame of `samples_per_frame` samples that the
-        next `count` samples from the current offset make up (the last one may be short):
-        true when every frame-slot of this stream the frame draws from is there and valid,
-        that is, when ``read(count)`` would fill none of its samples.  From the headers
-        alone (scan and index); nothing is decoded, the offset stays.
-
-        The call stands in for the read: where ``read(count)`` under ``verify='fix'``
-        would locate the frames of a damaged file, so does this (and the answer is that
-        of the read which follows); where it would raise under ``verify=True``, this
-        raises the same."""
-        if self.closed:
-            raise ValueError("I/O operation on closed stream.")
-        if count < 0 or count > self.shape[0] - self.offset:
-            raise EOFError("cannot read from beyond end of input.")
-        nout = -(-count // samples_per_frame)
-        if self._states_geometry() is None or count == 0:   # (no index of payloads: nothing known to be missing)
-            return np.ones(nout, bool)
-
-        def answer():
-            self._packed_request(count)
-            kernels.require_gpu()
-            spf = self.samples_per_frame
-            start, stop = self.offset, self.offset + count
-            marks = torch.zeros(nout + 1, dtype=torch.int32, device='cuda')
-            nbad = self._walk_packed(
-                start // spf, -(-stop // spf),
-                lambda dbuf, src, s, e: self._mark_invalid(marks, src, s, e, start, stop, samples_per_frame),
-                strict=True)
-            return (torch.cumsum(marks, 0)[:nout] == 0).cpu().numpy(), nbad
-
-        return self._answer_packed(answer, strict=True)
-
-    def read_packed(self, count, coder, nthread, nchan, samples_per_frame, fill_code):
-        """The next `count` samples as packed payloads of another frame geometry, without
-        decoding them (bb_repack_frames) -> ``(payloads, valid)``: a uint8 device tensor of
-        shape ``(count // samples_per_frame, nthread, payload_nbytes)`` holding what a
-        stream writer of `coder` (``_lib.CODER_*``) with `nthread` threads of `nchan`
-        channels and `samples_per_frame` samples per frame would encode ``read(count)``
-        to, and a host bool array, true where every frame-slot of this stream that an
-        output frame draws from is there and valid.  Samples of the others hold
-        `fill_code`.  `count` is a whole number of output frames; the offset must lie on a
-        byte boundary of a thread's stream on both sides.  Threads follow the reader's
-        selection; a channel `subset` is not applied.  Advances the offset.
-
-        A read in every respect but the decoding: a damaged file is repaired under
-        ``verify='fix'`` as ``read(count)`` repairs it (the frames are located and the
-        whole request is answered through that index), and ``verify=True`` raises what
-        ``read(count)`` raises; the offset then stays."""
-        count = operator.index(count)
-        if self.closed:
-            raise ValueError("I/O operation on closed stream.")
-        if self._states_geometry() is None:
-            raise NotImplementedError("{} has no packed reads".format(type(self).__name__))
-        self._packed_request(count)
-        coder_in, bps, chunk_in, nslot_in, payload_in = self._states_geometry()
-        chunk_out = nchan * (2 if self.complex_data else 1)
-        if count % samples_per_frame:
-            raise ValueError("read_packed: count must be a whole number of frames of {} samples"
-                             .format(samples_per_frame))
-        if samples_per_frame * chunk_out * bps % 32:
-            raise ValueError("read_packed: payloads are whole 32-bit words")
-        payload_out = samples_per_frame * chunk_out * bps // 8
-        if not kernels.repack_supported(bps, coder_in, coder, chunk_in, nslot_in, chunk_out, nthread,
-                                        payload_in, payload_out):
-            raise NotImplementedError(
-                "read_packed: {} x {} codes of {} bits (coder {}) -> {} x {} (coder {}) is not a conversion the "
-                "repack kernel takes".format(nslot_in, chunk_in, bps, coder_in, nthread, chunk_out, coder))
-        whole = max(1, 8 // (min(chunk_in, chunk_out) * bps))       # samples in a byte of a thread's stream
-        if self.offset % whole:
-            raise ValueError("read_packed: whole bytes only: seek to a multiple of {} samples".format(whole))
-        kernels.require_gpu()
-        nout = count // samples_per_frame
-        if count == 0:
-            return torch.empty((0, nthread, payload_out), dtype=torch.uint8, device='cuda'), np.ones(0, bool)
-
-        def answer():
-            self._packed_request(count)
-            out = torch.empty((nout, nthread, payload_out), dtype=torch.uint8, device='cuda')
-            spf = self.samples_per_frame
-            start, stop = self.offset, self.offset + count
-            marks = torch.zeros(nout + 1, dtype=torch.int32, device='cuda')
-
-            def visit(dbuf, src, s, e):
-                lo = max(start, s * spf)
-                kernels.repack_frames(dbuf, e - s, payload_in, bps, coder_in, chunk_in, nslot_in, coder, chunk_out,
-                                      nthread, payload_out, fill_code=fill_code, src=src, row_lo=lo - s * spf,
-                                      row_hi=min(stop, e * spf) - s * spf, first_row=lo - start, out=out.reshape(-1))
-                self._mark_invalid(marks, src, s, e, start, stop, samples_per_frame)
-
-            nbad = self._walk_packed(start // spf, -(-stop // spf), visit, strict=True)
-            return (out, (torch.cumsum(marks, 0)[:nout] == 0).cpu().numpy()), nbad
-
-        out, valid = self._answer_packed(answer, strict=True)
-        self.offset += count
-        return out, valid
 
     # ``host_results = True``: ``read()`` without `out` returns NEW NumPy arrays, as the
     # reference does (what the ``baseband.io`` plugin modules switch on): arrays on pinned

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib, kernels
+from .base.packed import samples_per_byte
 
 __all__ = ['convert']
 
@@ -53,7 +54,7 @@ def _packed_plan(fr, fw):
     if not isinstance(fr, (VDIFStreamReader, Mark5BStreamReader)) or layout is None:
         return "both ends must be VDIF or Mark 5B streams ({} -> {})".format(type(fr).__name__, type(fw).__name__), None
     coder_out, nthread, nchan = layout
-    coder_in, bps, chunk_in, nslot_in, payload_in = fr._states_geometry()
+    coder_in, bps, chunk_in, nslot_in, payload_in = fr._packed_geometry()
     if fw.bps != bps:
         return "bits per sample differ ({} -> {})".format(bps, fw.bps), None
     if bool(fw.complex_data) != bool(fr.complex_data):
@@ -72,7 +73,7 @@ def _packed_plan(fr, fw):
         return "the repack kernel does not take this pair of coders and frame geometries", None
     if fw._npending:
         return "the writer holds a partial frame", None
-    whole = max(1, 8 // (min(chunk_in, chunk_out) * bps))
+    whole = samples_per_byte(min(chunk_in, chunk_out), bps)
     if fr.offset % whole or spf % whole:
         return "the offset is not on a byte boundary of a thread's stream (a multiple of {} samples)".format(whole), None
     fill = _fill_code(fr.fill_value, coder_out, bps)

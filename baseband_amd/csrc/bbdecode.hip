@@ -364,6 +364,40 @@ inline int fixed_stride_check(int64_t src0, int64_t stride, uint64_t align, uint
     return BB_OK;
 }
 
+// ---- what the packed-byte entries (statistics, repack) ask of their arguments --------
+// A slot's stream of rows: payloads of whole dwords that hold whole rows of `chunk` codes
+// of `bps` bits (both checked by the caller) -> *R rows in a payload.
+inline int slot_rows(uint64_t payload_nbytes, int bps, int chunk, uint64_t *R)
+{
+    if (payload_nbytes == 0 || (payload_nbytes & 3) || payload_nbytes > (1ull << 56)) return BB_EINVAL;
+    const uint64_t codes = payload_nbytes * 8 / (uint64_t)bps;
+    *R = codes / (uint64_t)chunk;
+    return codes % (uint64_t)chunk ? BB_EINVAL : BB_OK;
+}
+
+// Rows [row_lo, row_hi) of `nframes` frame(set)s of R rows each; *empty: nothing is asked
+// for, which is BB_OK whatever the buffers are.
+inline int rows_check(size_t nframes, uint64_t R, uint64_t row_lo, uint64_t row_hi, bool *empty)
+{
+    if ((nframes && R > (~0ull) / (uint64_t)nframes) || row_hi > (uint64_t)nframes * R) return BB_ERANGE;
+    *empty = nframes == 0 || row_lo == row_hi;
+    return BB_OK;
+}
+
+// The source: `n` payloads of `span` bytes of the buffer, through the index or at the fixed
+// stride -> the source members of a kernel's arguments (every bb_*_args names them alike).
+template <class Args>
+inline int packed_source(Args &a, const void *d_buf, size_t buf_nbytes, const int64_t *d_src,
+                         int64_t src0, int64_t src_stride, uint64_t n, uint64_t span)
+{
+    if (!d_buf || ((uintptr_t)d_buf & 3)) return BB_EINVAL;
+    a.buf = (const uint8_t *)d_buf;
+    a.src = d_src;
+    a.src_lim = src_limit(buf_nbytes, span);
+    a.src0 = src0; a.src_stride = src_stride;
+    return d_src ? BB_OK : fixed_stride_check(src0, src_stride, 4, n, span, buf_nbytes);
+}
+
 // (bits per sample, coder) -> kernel template arguments <BPS, LV>
 template <class F>
 inline void with_levels(int bps, int coder, F &&f)
@@ -1572,20 +1606,19 @@ int bb_copy_frames(const void *d_buf, size_t buf_nbytes, size_t nframes, uint64_
 }
 
 // ---- sampler statistics (k_states.h).  EXTENSION: no reference counterpart. ----
-static int states_params_check(const bb_states_params *p)
+static int states_params_check(const bb_states_params *p, uint64_t *R)
 {
     if (!p) return BB_EINVAL;
     if (log2_bps(p->bps) < 0) return BB_ENOTSUP;
     if (p->reserved != 0 || p->nslot < 1 || p->chunk < 1) return BB_EINVAL;
     if (p->chunk & (p->chunk - 1)) return BB_ENOTSUP;
     if ((int64_t)p->chunk * p->bps > 8 * (int64_t)BB_STATES_MAX_PHASES) return BB_ENOTSUP;   // the byte phases kept on chip
-    if (p->payload_nbytes == 0 || (p->payload_nbytes & 3) || p->payload_nbytes > (1ull << 56)) return BB_EINVAL;
-    if ((p->payload_nbytes * 8 / (uint64_t)p->bps) % (uint64_t)p->chunk) return BB_EINVAL;   // whole rows
+    if (slot_rows(p->payload_nbytes, p->bps, p->chunk, R)) return BB_EINVAL;
     if (p->row_lo > p->row_hi) return BB_EINVAL;
     return BB_OK;
 }
 
-int bb_count_states_check(const bb_states_params *p) { return states_params_check(p); }
+int bb_count_states_check(const bb_states_params *p) { uint64_t R; return states_params_check(p, &R); }
 
 #define BB_STATES_GRID 2048ull                       // workgroups: what 256 CUs hold at once; each flushes once
 #define BB_STATES_WAVE_ITEMS (1ull << 19)            // work items a wave may see: 2^31 bytes, its 32-bit counters cannot wrap
@@ -1593,27 +1626,19 @@ int bb_count_states_check(const bb_states_params *p) { return states_params_chec
 int bb_count_states(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size_t nframes,
                     const bb_states_params *p, unsigned long long *d_counts, size_t ncounts, void *stream)
 {
-    int rc = states_params_check(p);
+    uint64_t R; bool empty;
+    int rc = states_params_check(p, &R);
     if (rc) return rc;
     if (!d_counts || ((uintptr_t)d_counts & 7)) return BB_EINVAL;
     const uint64_t nbins = ((uint64_t)p->nslot * (uint64_t)p->chunk) << p->bps;
     if (ncounts < nbins) return BB_ERANGE;
-    const uint64_t R = p->payload_nbytes * 8 / (uint64_t)p->bps / (uint64_t)p->chunk;
-    if (nframes && R > (~0ull) / (uint64_t)nframes) return BB_ERANGE;
-    if (p->row_hi > (uint64_t)nframes * R) return BB_ERANGE;
-    if (nframes == 0 || p->row_lo == p->row_hi) return BB_OK;
-    if (!d_buf || ((uintptr_t)d_buf & 3)) return BB_EINVAL;
-    const uint64_t nfs = (uint64_t)nframes * (uint64_t)p->nslot;
-    if (!d_src) {
-        rc = fixed_stride_check(p->src0, p->src_stride, 4, nfs, p->payload_nbytes, buf_nbytes);
-        if (rc) return rc;
-    }
+    rc = rows_check(nframes, R, p->row_lo, p->row_hi, &empty);
+    if (rc || empty) return rc;
     bb_states_args a;
-    a.buf = (const uint8_t *)d_buf;
-    a.src = d_src;
+    rc = packed_source(a, d_buf, buf_nbytes, d_src, p->src0, p->src_stride,
+                       (uint64_t)nframes * (uint64_t)p->nslot, p->payload_nbytes);
+    if (rc) return rc;
     a.counts = d_counts;
-    a.src_lim = src_limit(buf_nbytes, p->payload_nbytes);
-    a.src0 = p->src0; a.src_stride = p->src_stride;
     a.payload = p->payload_nbytes;
     a.R = R;
     a.row_lo = p->row_lo; a.row_hi = p->row_hi;
@@ -1643,9 +1668,9 @@ int bb_count_states(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, 
 }
 
 // ---- ... per time bin (k_state_bins.h) ----
-static int state_bins_params_check(const bb_states_params *p, uint64_t bin_rows)
+static int state_bins_params_check(const bb_states_params *p, uint64_t bin_rows, uint64_t *R)
 {
-    int rc = states_params_check(p);
+    int rc = states_params_check(p, R);
     if (rc) return rc;
     if (bin_rows == 0 || bin_rows > 0x7fffffffull) return BB_EINVAL;          // a counter never exceeds bin_rows: int32 holds it
     if ((bin_rows * (uint64_t)p->chunk * (uint64_t)p->bps) & 7) return BB_ENOTSUP;   // bins are whole bytes
@@ -1653,7 +1678,11 @@ static int state_bins_params_check(const bb_states_params *p, uint64_t bin_rows)
     return BB_OK;
 }
 
-int bb_count_states_bins_check(const bb_states_params *p, uint64_t bin_rows) { return state_bins_params_check(p, bin_rows); }
+int bb_count_states_bins_check(const bb_states_params *p, uint64_t bin_rows)
+{
+    uint64_t R;
+    return state_bins_params_check(p, bin_rows, &R);
+}
 
 #define BB_BINS_GRID 1280ull                         // workgroups: what 256 CUs hold at once with 32 KiB of LDS each
 
@@ -1661,7 +1690,8 @@ int bb_count_states_bins(const void *d_buf, size_t buf_nbytes, const int64_t *d_
                          const bb_states_params *p, uint64_t bin_rows, uint64_t first_row, uint64_t nbins,
                          uint32_t *d_counts, size_t ncounts, void *stream)
 {
-    int rc = state_bins_params_check(p, bin_rows);
+    uint64_t R; bool empty;
+    int rc = state_bins_params_check(p, bin_rows, &R);
     if (rc) return rc;
     if (!d_counts || ((uintptr_t)d_counts & 3)) return BB_EINVAL;
     const uint64_t cb = (uint64_t)p->chunk * (uint64_t)p->bps;                // bits per row, at most 128
@@ -1669,24 +1699,16 @@ int bb_count_states_bins(const void *d_buf, size_t buf_nbytes, const int64_t *d_
     if (((first_row * cb) | ((p->row_lo & 7) * cb) | ((p->row_hi & 7) * cb)) & 7) return BB_ENOTSUP;   // whole bytes only
     const uint64_t nc = (uint64_t)p->chunk << p->bps;                         // counters per bin and slot
     if (nbins > (~0ull) / (nc * (uint64_t)p->nslot) || ncounts < nbins * nc * (uint64_t)p->nslot) return BB_ERANGE;
-    const uint64_t R = p->payload_nbytes * 8 / (uint64_t)p->bps / (uint64_t)p->chunk;
-    if (nframes && (R > (~0ull) / (uint64_t)nframes || p->payload_nbytes > (1ull << 62) / (uint64_t)nframes)) return BB_ERANGE;
-    if (p->row_hi > (uint64_t)nframes * R) return BB_ERANGE;
-    if (nframes == 0 || p->row_lo == p->row_hi) return BB_OK;
+    if (nframes && p->payload_nbytes > (1ull << 62) / (uint64_t)nframes) return BB_ERANGE;
+    rc = rows_check(nframes, R, p->row_lo, p->row_hi, &empty);
+    if (rc || empty) return rc;
     if (p->row_hi - p->row_lo > (~0ull) - first_row) return BB_ERANGE;
     if ((first_row + (p->row_hi - 1 - p->row_lo)) / bin_rows >= nbins) return BB_ERANGE;   // the last counted row's bin
-    if (!d_buf || ((uintptr_t)d_buf & 3)) return BB_EINVAL;
-    const uint64_t nfs = (uint64_t)nframes * (uint64_t)p->nslot;
-    if (!d_src) {
-        rc = fixed_stride_check(p->src0, p->src_stride, 4, nfs, p->payload_nbytes, buf_nbytes);
-        if (rc) return rc;
-    }
     bb_state_bins_args a;
-    a.buf = (const uint8_t *)d_buf;
-    a.src = d_src;
+    rc = packed_source(a, d_buf, buf_nbytes, d_src, p->src0, p->src_stride,
+                       (uint64_t)nframes * (uint64_t)p->nslot, p->payload_nbytes);
+    if (rc) return rc;
     a.counts = d_counts;
-    a.src_lim = src_limit(buf_nbytes, p->payload_nbytes);
-    a.src0 = p->src0; a.src_stride = p->src_stride;
     a.payload = p->payload_nbytes;
     // rows -> bytes of a slot's stream (R * cb / 8 = payload: a frame begins on a byte)
     a.lo_byte = (p->row_lo / R) * a.payload + (p->row_lo % R) * cb / 8;
@@ -1736,7 +1758,7 @@ static int repack_code_map(int coder_in, int coder_out, int bps)
     return -1;                                              // VDIF <-> INT needs rescaling
 }
 
-static int repack_params_check(const bb_repack_params *p)
+static int repack_params_check(const bb_repack_params *p, uint64_t *R_in, uint64_t *R_out)
 {
     if (!p) return BB_EINVAL;
     if (log2_bps(p->bps) < 0) return BB_ENOTSUP;
@@ -1747,50 +1769,42 @@ static int repack_params_check(const bb_repack_params *p)
     if ((int64_t)p->nslot_in * p->chunk_in != (int64_t)p->nslot_out * p->chunk_out) return BB_EINVAL;
     if ((uint32_t)p->nslot_in > BB_REPACK_MAX_SLOTS || (uint32_t)p->nslot_out > BB_REPACK_MAX_SLOTS) return BB_ENOTSUP;
     if ((int64_t)p->nslot_in * p->chunk_in * p->bps > (int64_t)BB_REPACK_MAX_ROW_BITS) return BB_ENOTSUP;
-    if (p->payload_in == 0 || (p->payload_in & 3) || p->payload_in > (1ull << 56)) return BB_EINVAL;
-    if (p->payload_out == 0 || (p->payload_out & 3) || p->payload_out > (1ull << 56)) return BB_EINVAL;
-    if ((p->payload_in * 8 / (uint64_t)p->bps) % (uint64_t)p->chunk_in) return BB_EINVAL;     // whole rows
-    if ((p->payload_out * 8 / (uint64_t)p->bps) % (uint64_t)p->chunk_out) return BB_EINVAL;
+    if (slot_rows(p->payload_in, p->bps, p->chunk_in, R_in) ||
+        slot_rows(p->payload_out, p->bps, p->chunk_out, R_out)) return BB_EINVAL;
     if (p->fill_code < 0 || p->fill_code >= (1 << p->bps)) return BB_EINVAL;
     if (p->row_lo > p->row_hi) return BB_EINVAL;
     return BB_OK;
 }
 
-int bb_repack_check(const bb_repack_params *p) { return repack_params_check(p); }
+int bb_repack_check(const bb_repack_params *p) { uint64_t R_in, R_out; return repack_params_check(p, &R_in, &R_out); }
 
 #define BB_REPACK_GRID 4096ull                       // workgroups: several rounds of what 256 CUs hold (4 each, 37 KiB of LDS)
 
 int bb_repack_frames(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size_t nframes,
                      const bb_repack_params *p, void *d_out, size_t out_nbytes, void *stream)
 {
-    int rc = repack_params_check(p);
+    uint64_t R_in, R_out; bool empty;
+    int rc = repack_params_check(p, &R_in, &R_out);
     if (rc) return rc;
     if (!d_out || ((uintptr_t)d_out & 15)) return BB_EINVAL;
     const uint64_t bi = (uint64_t)p->chunk_in * (uint64_t)p->bps, bo = (uint64_t)p->chunk_out * (uint64_t)p->bps;   // bits per row and slot
     if (p->first_row > (1ull << 56)) return BB_ERANGE;
     if ((((p->row_lo & 7) | (p->row_hi & 7) | (p->first_row & 7)) * (bi | bo)) & 7) return BB_ENOTSUP;   // whole bytes only (bi, bo are powers of two)
-    const uint64_t R_in = p->payload_in * 8 / bi, R_out = p->payload_out * 8 / bo;
-    if (nframes && (R_in > (~0ull) / (uint64_t)nframes || p->payload_in > (1ull << 58) / (uint64_t)nframes)) return BB_ERANGE;
-    if (p->row_hi > (uint64_t)nframes * R_in) return BB_ERANGE;
-    if (nframes == 0 || p->row_lo == p->row_hi) return BB_OK;
+    if (nframes && p->payload_in > (1ull << 58) / (uint64_t)nframes) return BB_ERANGE;
+    rc = rows_check(nframes, R_in, p->row_lo, p->row_hi, &empty);
+    if (rc || empty) return rc;
     const uint64_t nrows = p->row_hi - p->row_lo;
     const uint64_t g_last = p->first_row + (nrows - 1);                       // the last output row, in slot nslot_out - 1
     const uint64_t f_last = g_last / R_out;
     if (f_last >= (1ull << 58) / (p->payload_out * (uint64_t)p->nslot_out)) return BB_ERANGE;
     if ((f_last * (uint64_t)p->nslot_out + (uint64_t)p->nslot_out - 1) * p->payload_out + ((g_last % R_out + 1) * bo + 7) / 8 > out_nbytes)
         return BB_ERANGE;
-    if (!d_buf || ((uintptr_t)d_buf & 3)) return BB_EINVAL;
-    if (!d_src) {
-        rc = fixed_stride_check(p->src0, p->src_stride, 4, (uint64_t)nframes * (uint64_t)p->nslot_in, p->payload_in, buf_nbytes);
-        if (rc) return rc;
-    }
     bb_repack_args a;
-    a.buf = (const uint8_t *)d_buf;
-    a.src = d_src;
+    rc = packed_source(a, d_buf, buf_nbytes, d_src, p->src0, p->src_stride,
+                       (uint64_t)nframes * (uint64_t)p->nslot_in, p->payload_in);
+    if (rc) return rc;
     a.out = (uint8_t *)d_out;
     a.buf_n = buf_nbytes;
-    a.src_lim = src_limit(buf_nbytes, p->payload_in);
-    a.src0 = p->src0; a.src_stride = p->src_stride;
     a.pay_in = p->payload_in; a.pay_out = p->payload_out;
     a.row_lo = p->row_lo; a.first_row = p->first_row; a.nrows = nrows;
     a.R_out = R_out;

@@ -558,10 +558,28 @@ def copy_frames(dbuf, nframes, nbytes_per_frame, src0=0, src_stride=0, out=None)
 STATES_MAX_ROW_BITS = 128      # chunk * bps the counting kernel takes (16 byte phases on chip)
 
 
+# -- what the calls on packed bytes share (count_states, count_states_bins, repack_frames)
+def _default_payload(bps, chunk):
+    """The smallest payload of whole dwords and rows: what `*_supported` asks about by default."""
+    return max(4, chunk * bps // 8) if bps in (1, 2, 4, 8) and chunk > 0 else 4
+
+
+def _all_rows(nframes, payload_nbytes, bps, chunk):
+    """The default `row_hi`: all rows of `nframes` frames (0 for a geometry the library will refuse)."""
+    return nframes * (payload_nbytes * 8 // bps // chunk) if bps in (1, 2, 4, 8) and chunk > 0 else 0
+
+
+def _given(tensor, name, dtype):
+    """Did the caller give the tensor that a call adds to or writes into?  Then it is contiguous and of `dtype`."""
+    if tensor is not None and (tensor.dtype != dtype or not tensor.is_contiguous()):
+        raise TypeError("{} must be a contiguous {} tensor".format(name, str(dtype).split('.')[-1]))
+    return tensor is not None
+
+
 def count_states_supported(bps, chunk=1, nslot=1, payload_nbytes=None):
     """Would `count_states` take this geometry?  (bb_count_states_check; no device needed.)"""
     if payload_nbytes is None:
-        payload_nbytes = max(4, chunk * bps // 8) if bps in (1, 2, 4, 8) else 4
+        payload_nbytes = _default_payload(bps, chunk)
     return _lib.count_states_check(bps, chunk, nslot, payload_nbytes) == _lib.BB_OK
 
 
@@ -574,19 +592,12 @@ def count_states(dbuf, nframes, payload_nbytes, bps, chunk=1, nslot=1, src=None,
     offset outside the buffer: not counted) or at ``src0 + k * src_stride``.  With `counts`
     (such a tensor, contiguous) the call ADDS to it.  Codes are raw: the level of code c is
     ``_lib.get_levels(coder, bps)[c]``.  Nothing is decoded and nothing synchronises."""
-    p = _lib.StatesParams()
-    p.bps, p.chunk, p.nslot, p.reserved = bps, chunk, nslot, 0
-    p.payload_nbytes = payload_nbytes
-    p.src0, p.src_stride = src0, src_stride
     if row_hi is None:
-        row_hi = nframes * (payload_nbytes * 8 // bps // chunk) if bps in (1, 2, 4, 8) and chunk > 0 else 0
-    p.row_lo, p.row_hi = row_lo, row_hi
-    if counts is None:
-        rc = lib.bb_count_states_check(C.byref(p))      # (before a shape is made of the parameters)
-        check(rc, 'bb_count_states')
+        row_hi = _all_rows(nframes, payload_nbytes, bps, chunk)
+    p = _lib.states_params(bps, chunk, nslot, payload_nbytes, src0, src_stride, row_lo, row_hi)
+    if not _given(counts, 'counts', torch.int64):
+        check(lib.bb_count_states_check(C.byref(p)), 'bb_count_states')     # (before a shape is made of the parameters)
         counts = torch.zeros((nslot, chunk, 1 << bps), dtype=torch.int64, device=dbuf.device)
-    elif counts.dtype != torch.int64 or not counts.is_contiguous():
-        raise TypeError("counts must be a contiguous int64 tensor")
     check(lib.bb_count_states(_ptr(dbuf), dbuf.numel(), _ptr(src), nframes, C.byref(p),
                               _ptr(counts), counts.numel(), _stream(dbuf)), 'bb_count_states')
     return counts
@@ -599,7 +610,7 @@ def count_states_bins_supported(bps, chunk=1, bin_rows=8, nslot=1, payload_nbyte
     """Would `count_states_bins` take this geometry and bin length?  (bb_count_states_bins_check;
     no device needed.)"""
     if payload_nbytes is None:
-        payload_nbytes = max(4, chunk * bps // 8) if bps in (1, 2, 4, 8) else 4
+        payload_nbytes = _default_payload(bps, chunk)
     if not 0 <= bin_rows < 1 << 64:
         return False
     return _lib.count_states_bins_check(bps, chunk, bin_rows, nslot, payload_nbytes) == _lib.BB_OK
@@ -613,19 +624,12 @@ def count_states_bins(dbuf, nframes, payload_nbytes, bps, chunk, nslot, bin_rows
     and the row range are whole bytes of a slot's stream.  With `counts` (such a tensor,
     contiguous) the call ADDS to it: windows of a file complete each other's bins.  Nothing
     is decoded and nothing synchronises."""
-    p = _lib.StatesParams()
-    p.bps, p.chunk, p.nslot, p.reserved = bps, chunk, nslot, 0
-    p.payload_nbytes = payload_nbytes
-    p.src0, p.src_stride = src0, src_stride
     if row_hi is None:
-        row_hi = nframes * (payload_nbytes * 8 // bps // chunk) if bps in (1, 2, 4, 8) and chunk > 0 else 0
-    p.row_lo, p.row_hi = row_lo, row_hi
-    if counts is None:
-        rc = lib.bb_count_states_bins_check(C.byref(p), bin_rows)     # (before a shape is made of the parameters)
-        check(rc, 'bb_count_states_bins')
+        row_hi = _all_rows(nframes, payload_nbytes, bps, chunk)
+    p = _lib.states_params(bps, chunk, nslot, payload_nbytes, src0, src_stride, row_lo, row_hi)
+    if not _given(counts, 'counts', torch.int32):
+        check(lib.bb_count_states_bins_check(C.byref(p), bin_rows), 'bb_count_states_bins')
         counts = torch.zeros((nslot, nbins, chunk, 1 << bps), dtype=torch.int32, device=dbuf.device)
-    elif counts.dtype != torch.int32 or not counts.is_contiguous():
-        raise TypeError("counts must be a contiguous int32 tensor")
     check(lib.bb_count_states_bins(_ptr(dbuf), dbuf.numel(), _ptr(src), nframes, C.byref(p), bin_rows, first_row,
                                    nbins, _ptr(counts), counts.numel(), _stream(dbuf)), 'bb_count_states_bins')
     return counts
@@ -638,11 +642,10 @@ REPACK_MAX_SLOTS = 32          # ... and thread slots on either side
 def repack_supported(bps, coder_in, coder_out, chunk_in, nslot_in, chunk_out, nslot_out,
                      payload_in=None, payload_out=None):
     """Would `repack_frames` take this conversion?  (bb_repack_check; no device needed.)"""
-    ok = bps in (1, 2, 4, 8)
     if payload_in is None:
-        payload_in = max(4, chunk_in * bps // 8) if ok and chunk_in > 0 else 4
+        payload_in = _default_payload(bps, chunk_in)
     if payload_out is None:
-        payload_out = max(4, chunk_out * bps // 8) if ok and chunk_out > 0 else 4
+        payload_out = _default_payload(bps, chunk_out)
     return _lib.repack_check(bps, coder_in, coder_out, chunk_in, nslot_in, chunk_out, nslot_out,
                              payload_in, payload_out) == _lib.BB_OK
 
@@ -660,16 +663,13 @@ def repack_frames(dbuf, nframes, payload_in, bps, coder_in, chunk_in, nslot_in, 
     of the rows written change.  The row range and `first_row` are whole bytes of every
     slot stream.  Nothing is decoded and nothing synchronises."""
     if row_hi is None:
-        row_hi = nframes * (payload_in * 8 // bps // chunk_in) if bps in (1, 2, 4, 8) and chunk_in > 0 else 0
+        row_hi = _all_rows(nframes, payload_in, bps, chunk_in)
     p = _lib.repack_params(bps, coder_in, coder_out, chunk_in, nslot_in, chunk_out, nslot_out, payload_in,
                            payload_out, fill_code, src0, src_stride, row_lo, row_hi, first_row)
-    if out is None:
-        check(lib.bb_repack_check(C.byref(p)), 'bb_repack_frames')   # (before a shape is made of the parameters)
-        r_out = payload_out * 8 // bps // chunk_out
-        nout = -(-(first_row + row_hi - row_lo) // r_out)
+    if not _given(out, 'out', torch.uint8):
+        check(lib.bb_repack_check(C.byref(p)), 'bb_repack_frames')
+        nout = -(-(first_row + row_hi - row_lo) // (payload_out * 8 // bps // chunk_out))     # whole output frames
         out = torch.empty(nout * nslot_out * payload_out, dtype=torch.uint8, device=dbuf.device)
-    elif out.dtype != torch.uint8 or not out.is_contiguous():
-        raise TypeError("out must be a contiguous uint8 tensor")
     check(lib.bb_repack_frames(_ptr(dbuf), dbuf.numel(), _ptr(src), nframes, C.byref(p),
                                _ptr(out), out.numel(), _stream(dbuf)), 'bb_repack_frames')
     return out

@@ -13,6 +13,7 @@ import torch
 from .. import _lib, kernels
 from ..base.base import (FileBase, VLBIFileReaderBase, GPUStreamReaderBase,
                          HeaderNotFoundError)
+from ..base.packed import PackedGeometry
 from ..base.header import strided_header_words
 from .header import Mark5BHeader, frame_header_words, crc16_mark5b
 from .frame import Mark5BFrame
@@ -220,12 +221,12 @@ class Mark5BStreamReader(GPUStreamReaderBase):
         return flat.reshape(((last - first) * self.samples_per_frame,)
                             + tuple(self._decode_shape))
 
-    # -- sampler statistics (base.state_counts)
-    def _states_geometry(self):
-        return (_lib.CODER_MARK5B, self.bps, self._unsliced_shape[0], 1, 10000)
+    # -- the packed bytes (base/packed.py: statistics, frames_valid, read_packed)
+    def _packed_geometry(self):
+        return PackedGeometry(_lib.CODER_MARK5B, self.bps, self._unsliced_shape[0], 1, 10000)
 
-    def _states_index(self, dbuf, first, nsets, verdict=None):
-        """`verdict` (base._WalkVerdict): the records are verified as `_process_window` has them
+    def _packed_index(self, dbuf, first, nsets, verdict=None):
+        """`verdict` (packed._WalkVerdict): the records are verified as `_process_window` has them
         verified -- every frame in place, the header behind the last one a header when `dbuf`
         holds it, frames the bytes do not reach counted as missing."""
         nframes = min(nsets + (1 if verdict is not None else 0), dbuf.numel() // FRAME_NBYTES)
@@ -239,7 +240,7 @@ class Mark5BStreamReader(GPUStreamReaderBase):
             kernels.verify_records(recs, nframes, 0, 1, min(nsets, nframes), verdict.counter)
         return kernels.build_index(recs, nsets, 1, None)
 
-    def _states_shape(self, counts):
+    def _packed_shape(self, counts):
         """(nchan, 2**bps)."""
         return counts[0]
 

@@ -16,6 +16,7 @@ import torch
 from .. import _lib, kernels
 from ..base.base import (FileBase, VLBIFileReaderBase, GPUStreamReaderBase,
                          HeaderNotFoundError)
+from ..base.packed import PackedGeometry
 from ..base.writer import GPUStreamWriterBase
 from ..base.opener import FormatOpener
 from ..base.header import strided_header_words
@@ -666,15 +667,15 @@ class VDIFStreamReader(GPUStreamReaderBase):
         if self.verify:
             self._note_checked(nframes, missing=nsets * nthread_file - nframes)
 
-    # -- sampler statistics (base.state_counts)
-    def _states_geometry(self):
+    # -- the packed bytes (base/packed.py: statistics, frames_valid, read_packed)
+    def _packed_geometry(self):
         h0 = self.header0
-        return (self._coder, self.bps, h0.nchan * (2 if self.complex_data else 1), len(self._thread_ids),
-                h0.payload_nbytes)
+        return PackedGeometry(self._coder, self.bps, h0.nchan * (2 if self.complex_data else 1),
+                              len(self._thread_ids), h0.payload_nbytes)
 
-    def _states_index(self, dbuf, first, nsets, verdict=None):
+    def _packed_index(self, dbuf, first, nsets, verdict=None):
         """The un-fused scan and index of `build_index` for the frame sets `dbuf` starts with.
-        `verdict` (base._WalkVerdict): the records are verified as `_process_window` has them
+        `verdict` (packed._WalkVerdict): the records are verified as `_process_window` has them
         verified -- every frame in place, frames the bytes do not reach counted as missing."""
         h0 = self.header0
         nslot = len(self._thread_ids)
@@ -693,7 +694,7 @@ class VDIFStreamReader(GPUStreamReaderBase):
             kernels.verify_records(recs, nframes, 0, nthread_file, nframes, verdict.counter)
         return kernels.build_index(recs, nsets, nslot, self._thread_slot)
 
-    def _states_shape(self, counts):
+    def _packed_shape(self, counts):
         """(nthread, nchan, 2**bps); complex data: (nthread, nchan, 2, 2**bps), (re, im)."""
         nchan = self.header0.nchan
         return counts.reshape((counts.shape[0], nchan) + ((2,) if self.complex_data else ()) + counts.shape[-1:])

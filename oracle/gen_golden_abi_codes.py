@@ -3,11 +3,14 @@
 replayed by tests/test_abi_codes.py.
 
 Run ONCE, at the commit whose answers are the expectation (the parent of a change to
-the host dispatch), on a machine WITHOUT a device: every check runs before the first
-HIP call, so a call with one fault answers its code there and a call without a fault
-stops at BB_EIO.  Device addresses are made up; nothing follows them on the host.
-The table holds single-fault calls only (with two faults either code is right), and
-only calls that answer something other than BB_EIO -- asserted below.
+the host dispatch; last: the parent of the change that gave the packed-byte entries
+bb_count_states, bb_count_states_bins and bb_repack_frames their shared checks), on a
+machine WITHOUT a device: every check runs before the first HIP call, so a call with
+one fault answers its code there and a call without a fault stops at BB_EIO.  Device
+addresses are made up; nothing follows them on the host.  The decode, encode, scan and
+window entries have single-fault calls only; the packed-byte entries also have one call
+per pair of checks that answer different codes, which holds their ORDER in place.  Only
+calls that answer something other than BB_EIO are recorded -- asserted below.
 
     python oracle/gen_golden_abi_codes.py
 """
@@ -450,16 +453,227 @@ add('buffer not 8-byte aligned', d_buf=BUF + 4)
 add('nothing to read', nframes=0, n=0)
 add('nothing to read, selecting', nframes=0, n=0, nout=4)
 
+# ---- the packed-byte entries: statistics and repack -----------------------------------------
+# Single faults as above, and DOUBLE faults: what a reordering of the checks would change
+# unseen.  A rule is (statement, label, changes): `statement` names the `if` of the entry
+# that answers it.  main() pairs the first rule of every statement with the first rule of
+# every other statement that answers another code (one call per pair of statements, not of
+# values); pairs whose changes contradict each other are left out, PAIRED_BY_HAND adds the
+# ones worth a call of their own.
+PAIRED = []                                                         # (fn, names, base, rules)
+
+
+def rules(fn, names, base, table):
+    add = entry(fn, names, base)
+    for _, label, changes in table:
+        add(label, **changes)
+    PAIRED.append((fn, names, base, table))
+    return add
+
+
+def states(**f):
+    d = dict(bps=2, chunk=1, nslot=1, reserved=0, payload_nbytes=192, src0=0, src_stride=192, row_lo=0, row_hi=8)
+    d.update(f)
+    return S('StatesParams', **d)
+
+
+# 4 frames of 192 bytes: 768 rows of one 2-bit code each; chunk 3 still makes whole rows
+STATES_RULES = [
+    ('bps', '3 bits per sample', dict(p__bps=3)),
+    ('fields', 'reserved set', dict(p__reserved=1)),
+    ('fields', 'nslot 0', dict(p__nslot=0)),
+    ('fields', 'chunk 0', dict(p__chunk=0)),
+    ('pow2', 'chunk not a power of two', dict(p__chunk=3)),
+    ('row bits', 'rows of more than 128 bits', dict(p__chunk=128)),
+    ('payload', 'payload not whole dwords', dict(p__payload_nbytes=190)),
+    ('payload', 'empty payload', dict(p__payload_nbytes=0)),
+    ('payload', 'payload above 2^56', dict(p__payload_nbytes=(1 << 56) + 4)),
+    ('whole rows', 'payload not whole rows', dict(p__payload_nbytes=196, p__chunk=32)),
+    ('row order', 'row_lo past row_hi', dict(p__row_lo=16)),
+]
+SOURCE_RULES = [
+    ('empty', 'no rows', dict(p__row_lo=8)),
+    ('empty', 'nframes 0', dict(nframes=0, p__row_hi=0)),
+    ('buffer', 'null buffer', dict(d_buf=None)),
+    ('buffer', 'buffer not 4-byte aligned', dict(d_buf=BUF + 2)),
+    ('stride', 'misaligned src0', dict(p__src0=2)),
+    ('stride', 'negative src0', dict(p__src0=-4)),
+    ('stride', 'misaligned src_stride', dict(p__src_stride=194)),
+    ('stride', 'negative src_stride', dict(p__src_stride=-192)),
+    ('source range', 'source range one byte past the end', dict(buf_nbytes=767)),
+]
+CS = ['d_buf', 'buf_nbytes', 'd_src', 'nframes', 'p', 'd_counts', 'ncounts', 'stream']
+add = rules('bb_count_states', CS,
+            dict(d_buf=BUF, buf_nbytes=768, d_src=None, nframes=4, p=states(), d_counts=CNT, ncounts=1024, stream=None),
+            STATES_RULES + [
+                ('counts', 'null counts', dict(d_counts=None)),
+                ('counts', 'counts not 8-byte aligned', dict(d_counts=CNT + 4)),
+                ('ncounts', 'counts one short', dict(ncounts=3)),
+                ('rows overflow', 'more rows than 64 bits count', dict(nframes=1 << 60)),
+                ('row range', 'row_hi past the last row', dict(p__row_hi=4 * 768 + 8)),
+            ] + SOURCE_RULES + [
+                ('work', 'more work items in a frame than 32 bits count', dict(d_src=SRC, p__payload_nbytes=1 << 50)),
+            ])
+add('null parameter block', p=None)
+add('nframes 0, null buffers', nframes=0, p__row_hi=0, d_buf=None, buf_nbytes=0)
+add('more workgroups than a grid holds', d_src=SRC, nframes=1 << 40, p__payload_nbytes=1 << 20, p__nslot=32,
+    p__row_hi=1 << 62)
+
+CSB = ['d_buf', 'buf_nbytes', 'd_src', 'nframes', 'p', 'bin_rows', 'first_row', 'nbins', 'd_counts', 'ncounts', 'stream']
+add = rules('bb_count_states_bins', CSB,
+            dict(d_buf=BUF, buf_nbytes=768, d_src=None, nframes=4, p=states(), bin_rows=4, first_row=0, nbins=2,
+                 d_counts=CNT, ncounts=1024, stream=None),
+            STATES_RULES + [
+                ('bin_rows', 'bin_rows 0', dict(bin_rows=0)),
+                ('bin_rows', 'bin_rows 2^31', dict(bin_rows=1 << 31)),
+                ('bin bytes', 'bins not whole bytes', dict(bin_rows=6)),
+                ('counters', 'more counters per bin than a window takes', dict(p__chunk=16, p__bps=8,
+                                                                               p__payload_nbytes=64, p__src_stride=64)),
+                ('counts', 'null counts', dict(d_counts=None)),
+                ('counts', 'counts not 4-byte aligned', dict(d_counts=CNT + 2)),
+                ('first_row', 'first_row above 2^56', dict(first_row=(1 << 56) + 8)),
+                ('whole bytes', 'first_row not a whole byte', dict(first_row=2)),
+                ('whole bytes', 'row_lo not a whole byte', dict(p__row_lo=2)),
+                ('whole bytes', 'row_hi not a whole byte', dict(p__row_hi=10)),
+                ('ncounts', 'counts one short', dict(ncounts=7)),
+                ('ncounts', 'more counters than 64 bits count', dict(nbins=1 << 62)),
+                ('rows overflow', 'more rows than 64 bits count', dict(nframes=1 << 60)),
+                ('rows overflow', 'more bytes than 2^62', dict(d_src=SRC, nframes=1 << 20, p__payload_nbytes=1 << 43)),
+                ('row range', 'row_hi past the last row', dict(p__row_hi=4 * 768 + 8)),
+            ] + SOURCE_RULES[:2] + [
+                ('last bin', 'the last row past the last bin', dict(nbins=1)),
+            ] + SOURCE_RULES[2:])
+add('null parameter block', p=None)
+add('nframes 0, null buffers', nframes=0, p__row_hi=0, d_buf=None, buf_nbytes=0)
+add('rows and first_row past 64 bits', d_src=SRC, nframes=(1 << 21) - 1, p__bps=1, p__payload_nbytes=1 << 40,
+    p__row_hi=((1 << 21) - 1) << 43, bin_rows=8, first_row=1 << 56, nbins=8)
+
+
+def repack(**f):
+    d = dict(bps=2, coder_in=0, coder_out=1, chunk_in=1, nslot_in=2, chunk_out=2, nslot_out=1, fill_code=0,
+             payload_in=192, payload_out=64, src0=0, src_stride=192, row_lo=0, row_hi=8, first_row=0, reserved=0)
+    d.update(f)
+    return S('RepackParams', **d)
+
+
+# 4 frame sets of 2 slots x 192 bytes (768 rows each) -> payloads of 64 bytes, 128 rows of 2 codes
+RP = ['d_buf', 'buf_nbytes', 'd_src', 'nframes', 'p', 'd_out', 'out_nbytes', 'stream']
+add = rules('bb_repack_frames', RP,
+            dict(d_buf=BUF, buf_nbytes=8 * 192, d_src=None, nframes=4, p=repack(), d_out=OUT, out_nbytes=1 << 16, stream=None),
+            [
+                ('bps', '3 bits per sample', dict(p__bps=3)),
+                ('fields', 'reserved set', dict(p__reserved=1)),
+                ('fields', 'chunk_in 0', dict(p__chunk_in=0)),
+                ('fields', 'nslot_in 0', dict(p__nslot_in=0)),
+                ('fields', 'chunk_out 0', dict(p__chunk_out=0)),
+                ('fields', 'nslot_out 0', dict(p__nslot_out=0)),
+                ('code map', 'VDIF to INT', dict(p__coder_out=2)),
+                ('code map', 'unknown coder', dict(p__coder_in=7)),
+                ('pow2', 'chunk_in not a power of two', dict(p__chunk_in=3, p__chunk_out=6)),
+                ('pow2', 'nslot_out not a power of two', dict(p__nslot_in=6, p__nslot_out=3)),
+                ('samples', 'complete samples differ', dict(p__chunk_out=4)),
+                ('slots', '64 slots in', dict(p__nslot_in=64, p__chunk_out=64)),
+                ('slots', '64 slots out', dict(p__nslot_out=64, p__chunk_in=64)),
+                ('row bits', 'rows of more than 256 bits', dict(p__chunk_in=128, p__nslot_out=8, p__chunk_out=32)),
+                ('payload in', 'payload_in not whole dwords', dict(p__payload_in=190)),
+                ('payload in', 'empty payload_in', dict(p__payload_in=0)),
+                ('payload in', 'payload_in above 2^56', dict(p__payload_in=(1 << 56) + 4)),
+                ('payload out', 'payload_out not whole dwords', dict(p__payload_out=62)),
+                ('payload out', 'empty payload_out', dict(p__payload_out=0)),
+                ('payload out', 'payload_out above 2^56', dict(p__payload_out=(1 << 56) + 4)),
+                ('whole rows in', 'payload_in not whole rows', dict(p__payload_in=196, p__chunk_in=32, p__chunk_out=64)),
+                ('whole rows out', 'payload_out not whole rows', dict(p__payload_out=68, p__chunk_in=16, p__chunk_out=32)),
+                ('fill', 'negative fill_code', dict(p__fill_code=-1)),
+                ('fill', 'fill_code 4', dict(p__fill_code=4)),
+                ('row order', 'row_lo past row_hi', dict(p__row_lo=16)),
+                ('output', 'null output', dict(d_out=None)),
+                ('output', 'output not 16-byte aligned', dict(d_out=OUT + 8)),
+                ('first_row', 'first_row above 2^56', dict(p__first_row=(1 << 56) + 8)),
+                ('whole bytes', 'first_row not a whole byte', dict(p__first_row=2)),
+                ('whole bytes', 'row_lo not a whole byte', dict(p__row_lo=2)),
+                ('whole bytes', 'row_hi not a whole byte', dict(p__row_hi=10)),
+                ('rows overflow', 'more rows than 64 bits count', dict(nframes=1 << 60)),
+                ('rows overflow', 'more bytes than 2^58', dict(d_src=SRC, nframes=1 << 20, p__payload_in=1 << 39)),
+                ('row range', 'row_hi past the last row', dict(p__row_hi=4 * 768 + 8)),
+                ('empty', 'no rows', dict(p__row_lo=8)),
+                ('empty', 'nframes 0', dict(nframes=0, p__row_hi=0)),
+                ('output frames', 'more output bytes than 2^58', dict(p__first_row=1 << 56, p__chunk_in=16, p__chunk_out=32)),
+                ('output range', 'output one byte short', dict(out_nbytes=3)),
+                ('buffer', 'null buffer', dict(d_buf=None)),
+                ('buffer', 'buffer not 4-byte aligned', dict(d_buf=BUF + 2)),
+                ('stride', 'misaligned src0', dict(p__src0=2)),
+                ('stride', 'negative src0', dict(p__src0=-4)),
+                ('stride', 'misaligned src_stride', dict(p__src_stride=194)),
+                ('stride', 'negative src_stride', dict(p__src_stride=-192)),
+                ('source range', 'source range one byte past the end', dict(buf_nbytes=8 * 192 - 1)),
+            ])
+add('null parameter block', p=None)
+add('nframes 0, null buffers', nframes=0, p__row_hi=0, d_buf=None, buf_nbytes=0)
+add('second output frame one byte short', p__first_row=128, out_nbytes=67)
+
+# pairs whose single-fault changes contradict each other, restated so that both faults stand
+PAIRED_BY_HAND = {
+    'bb_count_states': [
+        ('empty + row range', dict(p__row_lo=4 * 768 + 8, p__row_hi=4 * 768 + 8)),
+        ('empty + row order (nframes 0)', dict(nframes=0, p__row_lo=8, p__row_hi=0)),
+        ('empty + row range (nframes 0)', dict(nframes=0)),
+    ],
+    'bb_count_states_bins': [
+        ('empty + row range', dict(p__row_lo=4 * 768 + 8, p__row_hi=4 * 768 + 8)),
+        ('empty + row range (nframes 0)', dict(nframes=0)),
+        ('empty + whole bytes', dict(p__row_lo=2, p__row_hi=2)),
+        ('whole bytes + row range', dict(p__row_hi=4 * 768 + 2)),
+        ('whole bytes + first_row', dict(first_row=(1 << 56) + 2)),
+    ],
+    'bb_repack_frames': [
+        ('empty + row range', dict(p__row_lo=4 * 768 + 8, p__row_hi=4 * 768 + 8)),
+        ('empty + row range (nframes 0)', dict(nframes=0)),
+        ('empty + whole bytes', dict(p__row_lo=2, p__row_hi=2)),
+        ('whole bytes + row range', dict(p__row_hi=4 * 768 + 2)),
+        ('whole bytes + first_row', dict(p__first_row=(1 << 56) + 2)),
+    ],
+}
+
+
+def pair_cases(code_of):
+    """The double-fault calls of PAIRED, given the codes the single faults answered."""
+    npairs = nskipped = 0
+    for fn, names, base, table in PAIRED:
+        add = entry(fn, names, base)
+        first = {}
+        for statement, label, changes in table:
+            first.setdefault(statement, (label, changes))
+        reps = list(first.items())
+        for i, (sa, (la, ca)) in enumerate(reps):
+            for sb, (lb, cb) in reps[i + 1:]:
+                if code_of['{}:{}'.format(fn, la)] == code_of['{}:{}'.format(fn, lb)]:
+                    continue
+                if any(k in cb and cb[k] != v for k, v in ca.items()):
+                    nskipped += 1
+                    continue
+                add('{} + {}'.format(la, lb), **dict(ca, **cb))
+                npairs += 1
+        for label, changes in PAIRED_BY_HAND[fn]:
+            add(label, **changes)
+    return npairs, nskipped
+
 
 def main():
     from baseband_amd import _lib
     assert abi_replay.device_is_hidden(), "record this table on a machine without a device"
+
+    def record(cases):
+        for c in cases:
+            c['code'] = abi_replay.call(c)
+            assert c['code'] != _lib.BB_EIO, "{}: passes its argument checks (BB_EIO): not a case for this table".format(c['id'])
+            assert c['code'] in (_lib.BB_OK, _lib.BB_EINVAL, _lib.BB_ERANGE, _lib.BB_ENOTSUP), c
+
+    record(CASES)
+    nsingle = len(CASES)
+    print("{} pairs of statements, {} left out (contradicting changes)".format(*pair_cases({c['id']: c['code'] for c in CASES})))
+    record(CASES[nsingle:])
     ids = [c['id'] for c in CASES]
     assert len(set(ids)) == len(ids), [i for i in ids if ids.count(i) > 1]
-    for c in CASES:
-        c['code'] = abi_replay.call(c)
-        assert c['code'] != _lib.BB_EIO, "{}: passes its argument checks (BB_EIO): not a case for this table".format(c['id'])
-        assert c['code'] in (_lib.BB_OK, _lib.BB_EINVAL, _lib.BB_ERANGE, _lib.BB_ENOTSUP), c
     path = os.path.join(ROOT, 'tests', 'golden', 'abi_return_codes.json')
     with open(path, 'w') as f:
         f.write('{"cases": [\n' + ',\n'.join(json.dumps(c, sort_keys=True) for c in CASES) + '\n]}\n')
