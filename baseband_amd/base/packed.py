@@ -354,7 +354,7 @@ class PackedBytesMixin:
 
         return self._answer_packed(answer, strict=True)
 
-    def read_packed(self, count, coder, nthread, nchan, samples_per_frame, fill_code):
+    def read_packed(self, count, coder, nthread, nchan, samples_per_frame, fill_code, bps=None, scale=None):
         """The next `count` samples as packed payloads of another frame geometry, without
         decoding them (bb_repack_frames) -> ``(payloads, valid)``: a uint8 device tensor of
         shape ``(count // samples_per_frame, nthread, payload_nbytes)`` holding what a
@@ -365,6 +365,13 @@ class PackedBytesMixin:
         `fill_code`.  `count` is a whole number of output frames; the offset must lie on a
         byte boundary of a thread's stream on both sides.  Threads follow the reader's
         selection; a channel `subset` is not applied.  Advances the offset.
+
+        With `bps` other than the reader's, or a `scale`, the samples are requantized on
+        the packed bytes (bb_requant_frames): every code goes through the table
+        ``kernels.requant_table(own coder, own bps, coder, bps, scale)``, which is decode,
+        times ``float32(scale)``, encode.  The thread structure must then be the same on
+        both sides (`nthread` threads of as many codes per sample as the reader's), else
+        NotImplementedError; `fill_code` is a code of `bps` bits and is not mapped.
 
         A read in every respect but the decoding: a damaged file is repaired under
         ``verify='fix'`` as ``read(count)`` repairs it (the frames are located and the
@@ -377,19 +384,31 @@ class PackedBytesMixin:
         if count % samples_per_frame:
             raise ValueError("read_packed: count must be a whole number of frames of {} samples"
                              .format(samples_per_frame))
-        if samples_per_frame * chunk_out * g.bps % 32:
+        requant = scale is not None or (bps is not None and bps != g.bps)
+        bps_out = g.bps if bps is None else operator.index(bps)
+        if samples_per_frame * chunk_out * bps_out % 32:
             raise ValueError("read_packed: payloads are whole 32-bit words")
-        payload_out = samples_per_frame * chunk_out * g.bps // 8
-        if not kernels.repack_supported(g.bps, g.coder, coder, g.chunk, g.nslot, chunk_out, nthread,
-                                        g.payload_nbytes, payload_out):
+        payload_out = samples_per_frame * chunk_out * bps_out // 8
+        if requant:
+            if nthread != g.nslot or chunk_out != g.chunk:
+                raise NotImplementedError(
+                    "read_packed: a change of sample width or scale keeps the thread structure ({} x {} codes "
+                    "-> {} x {})".format(g.nslot, g.chunk, nthread, chunk_out))
+            if not kernels.requant_supported(g.bps, bps_out, g.chunk, g.nslot, g.payload_nbytes, payload_out):
+                raise NotImplementedError(
+                    "read_packed: {} x {} codes of {} bits -> {} bits is not a conversion the requantize "
+                    "kernel takes".format(g.nslot, g.chunk, g.bps, bps_out))
+        elif not kernels.repack_supported(g.bps, g.coder, coder, g.chunk, g.nslot, chunk_out, nthread,
+                                          g.payload_nbytes, payload_out):
             raise NotImplementedError(
                 "read_packed: {} x {} codes of {} bits (coder {}) -> {} x {} (coder {}) is not a conversion the "
                 "repack kernel takes".format(g.nslot, g.chunk, g.bps, g.coder, nthread, chunk_out, coder))
-        whole = samples_per_byte(min(g.chunk, chunk_out), g.bps)
+        whole = samples_per_byte(min(g.chunk, chunk_out), min(g.bps, bps_out))
         if self.offset % whole:
             raise ValueError("read_packed: whole bytes only: seek to a multiple of {} samples".format(whole))
         kernels.require_gpu()
         nout = count // samples_per_frame
+        table = kernels.requant_table(g.coder, g.bps, coder, bps_out, scale) if requant else None
         if count == 0:
             return torch.empty((0, nthread, payload_out), dtype=torch.uint8, device='cuda'), np.ones(0, bool)
 
@@ -400,9 +419,14 @@ class PackedBytesMixin:
             marks = _ValidityMarks(nout, samples_per_frame, start, stop, self.samples_per_frame, g.nslot)
 
             def visit(dbuf, src, s, e, row_lo, row_hi, first_row):
-                kernels.repack_frames(dbuf, e - s, g.payload_nbytes, g.bps, g.coder, g.chunk, g.nslot, coder, chunk_out,
-                                      nthread, payload_out, fill_code=fill_code, src=src, row_lo=row_lo,
-                                      row_hi=row_hi, first_row=first_row, out=out.reshape(-1))
+                if requant:
+                    kernels.requant_frames(dbuf, e - s, g.payload_nbytes, g.bps, g.chunk, g.nslot, bps_out, payload_out,
+                                           table, fill_code=fill_code, src=src, row_lo=row_lo, row_hi=row_hi,
+                                           first_row=first_row, out=out.reshape(-1))
+                else:
+                    kernels.repack_frames(dbuf, e - s, g.payload_nbytes, g.bps, g.coder, g.chunk, g.nslot, coder,
+                                          chunk_out, nthread, payload_out, fill_code=fill_code, src=src,
+                                          row_lo=row_lo, row_hi=row_hi, first_row=first_row, out=out.reshape(-1))
                 marks.add(src, s, e)
 
             nbad = self._walk_packed(g.nslot, start, stop, visit, strict=True)

@@ -15,6 +15,7 @@
 #include "k_states.h"
 #include "k_state_bins.h"
 #include "k_repack.h"
+#include "k_requant.h"
 #include "k_tfpick.h"
 #if BB_EXP
 #include "k_burst.h"
@@ -1827,6 +1828,76 @@ int bb_repack_frames(const void *d_buf, size_t buf_nbytes, const int64_t *d_src,
     return BB_OK;
 }
 
+// ---- conversion between sample widths on the packed bytes (k_requant.h): decode, one gain and
+//      encode of base/payload.py:314-330, vdif/payload.py:25-114, mark5b/payload.py:27-106 as a table ----
+static int requant_params_check(const bb_requant_params *p, uint64_t *R_in, uint64_t *R_out)
+{
+    if (!p) return BB_EINVAL;
+    if (log2_bps(p->bps_in) < 0 || log2_bps(p->bps_out) < 0) return BB_ENOTSUP;
+    if (p->reserved != 0 || p->chunk < 1 || p->nslot < 1) return BB_EINVAL;
+    if ((p->chunk & (p->chunk - 1)) || (p->nslot & (p->nslot - 1))) return BB_ENOTSUP;
+    if ((uint32_t)p->nslot > BB_REQUANT_MAX_SLOTS) return BB_ENOTSUP;
+    if ((int64_t)p->chunk * std::max(p->bps_in, p->bps_out) > (int64_t)BB_REQUANT_MAX_ROW_BITS) return BB_ENOTSUP;
+    if (slot_rows(p->payload_in, p->bps_in, p->chunk, R_in) ||
+        slot_rows(p->payload_out, p->bps_out, p->chunk, R_out)) return BB_EINVAL;
+    if (p->fill_code < 0 || p->fill_code >= (1 << p->bps_out)) return BB_EINVAL;
+    for (int c = 0; c < (1 << p->bps_in); ++c)
+        if ((int)p->map[c] >= (1 << p->bps_out)) return BB_EINVAL;
+    if (p->row_lo > p->row_hi) return BB_EINVAL;
+    return BB_OK;
+}
+
+int bb_requant_check(const bb_requant_params *p) { uint64_t R_in, R_out; return requant_params_check(p, &R_in, &R_out); }
+
+#define BB_REQUANT_GRID 4096ull                      // workgroups: several rounds of what 256 CUs hold
+
+int bb_requant_frames(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size_t nframes,
+                      const bb_requant_params *p, void *d_out, size_t out_nbytes, void *stream)
+{
+    uint64_t R_in, R_out; bool empty;
+    int rc = requant_params_check(p, &R_in, &R_out);
+    if (rc) return rc;
+    if (!d_out || ((uintptr_t)d_out & 15)) return BB_EINVAL;
+    const uint64_t bi = (uint64_t)p->chunk * (uint64_t)p->bps_in, bo = (uint64_t)p->chunk * (uint64_t)p->bps_out;   // bits per row and slot
+    if (p->first_row > (1ull << 56)) return BB_ERANGE;
+    if ((((p->row_lo & 7) | (p->row_hi & 7) | (p->first_row & 7)) * (bi | bo)) & 7) return BB_ENOTSUP;   // whole bytes only (bi, bo are powers of two)
+    if (nframes && p->payload_in > (1ull << 58) / (uint64_t)nframes) return BB_ERANGE;
+    rc = rows_check(nframes, R_in, p->row_lo, p->row_hi, &empty);
+    if (rc || empty) return rc;
+    const uint64_t nrows = p->row_hi - p->row_lo;
+    const uint64_t g_last = p->first_row + (nrows - 1);                       // the last output row, in slot nslot - 1
+    const uint64_t f_last = g_last / R_out;
+    if (f_last >= (1ull << 58) / (p->payload_out * (uint64_t)p->nslot)) return BB_ERANGE;
+    if ((f_last * (uint64_t)p->nslot + (uint64_t)p->nslot - 1) * p->payload_out + ((g_last % R_out + 1) * bo + 7) / 8 > out_nbytes)
+        return BB_ERANGE;
+    bb_requant_args a;
+    rc = packed_source(a, d_buf, buf_nbytes, d_src, p->src0, p->src_stride,
+                       (uint64_t)nframes * (uint64_t)p->nslot, p->payload_in);
+    if (rc) return rc;
+    a.out = (uint8_t *)d_out;
+    a.buf_n = buf_nbytes;
+    a.pay_in = p->payload_in; a.pay_out = p->payload_out;
+    // rows -> bytes of a slot's output stream and bits of its input stream (R * bo / 8 = payload_out: a frame begins on a byte)
+    a.ya = (p->first_row / R_out) * a.pay_out + (p->first_row % R_out) * bo / 8;
+    a.yb = a.ya + ((nrows / 8) * bo + (nrows % 8) * bo / 8);
+    a.xbit_a = p->row_lo * bi;
+    a.F0 = p->first_row / R_out;
+    a.nslot = (uint32_t)p->nslot;
+    a.lbi = (uint32_t)log2_bps(p->bps_in); a.lbo = (uint32_t)log2_bps(p->bps_out);
+    a.seg = a.lbi > a.lbo ? BB_REQUANT_ITEM_BYTES >> (a.lbi - a.lbo) : BB_REQUANT_ITEM_BYTES;
+    a.nseg = (a.pay_out + a.seg - 1) / a.seg;
+    const uint64_t nf = f_last - a.F0 + 1;
+    if (nf > (~0ull) / (a.nseg * a.nslot)) return BB_ERANGE;
+    a.nwork = nf * a.nseg * a.nslot;
+    a.fillw = (uint32_t)p->fill_code * (0xffffffffu / ((1u << p->bps_out) - 1u));
+    uint8_t *m = reinterpret_cast<uint8_t *>(a.map);                          // (entries the input cannot have: 0)
+    for (int c = 0; c < 256; ++c) m[c] = c < (1 << p->bps_in) ? p->map[c] : 0;
+    const dim3 grid = capped_grid((a.nwork + BB_WAVES_PER_BLOCK - 1) / BB_WAVES_PER_BLOCK, BB_REQUANT_GRID);
+    hipLaunchKernelGGL(k_requant, grid, dim3(BB_BLOCK), 0, (hipStream_t)stream, a);
+    BB_HIP(hipGetLastError());
+    return BB_OK;
+}
+
 int bb_decode_frames_select_check(const bb_decode_params *p, int nwithin)
 {
     select_geom g;
@@ -1991,11 +2062,8 @@ int bb_mark4_header_crc(const void *d_buf, size_t nbytes, int ntrack, const int6
     const dim3 block(BB_BLOCK);
     hipStream_t st = (hipStream_t)stream;
     const uint8_t *b = (const uint8_t *)d_buf;
-    switch (ntrack) {
-        case 16: hipLaunchKernelGGL(k_mark4_header_crc<16>, grid, block, 0, st, b, (uint64_t)nbytes, d_offsets, first_offset, (uint64_t)nframes, d_bad_tracks); break;
-        case 32: hipLaunchKernelGGL(k_mark4_header_crc<32>, grid, block, 0, st, b, (uint64_t)nbytes, d_offsets, first_offset, (uint64_t)nframes, d_bad_tracks); break;
-        default: hipLaunchKernelGGL(k_mark4_header_crc<64>, grid, block, 0, st, b, (uint64_t)nbytes, d_offsets, first_offset, (uint64_t)nframes, d_bad_tracks); break;
-    }
+    hipLaunchKernelGGL(k_mark4_header_crc, grid, block, 0, st, b, (uint64_t)nbytes, (uint32_t)ntrack, d_offsets, first_offset,
+                       (uint64_t)nframes, d_bad_tracks);
     BB_HIP(hipGetLastError());
     return BB_OK;
 }

@@ -175,13 +175,10 @@ void k_mark4_scan(const uint8_t *buf, uint64_t nbytes, bb_mark4_scan_params p,
 // the reference: twelve NTRACK-bit registers hold one remainder bit of every
 // track each; one thread walks the 160 stream words of one frame.
 template <int NTRACK>
-__global__ __launch_bounds__(BB_BLOCK)
-void k_mark4_header_crc(const uint8_t *buf, uint64_t nbytes, const int64_t *offsets,
-                        int64_t first_offset, uint64_t nframes, uint64_t *bad_tracks)
+__device__ __forceinline__ void bb_m4_header_crc(const uint8_t *buf, uint64_t nbytes, const int64_t *offsets,
+                                                 int64_t first_offset, uint64_t f, uint64_t *bad_tracks)
 {
     typedef typename bb_m4_word<NTRACK>::type word_t;
-    const uint64_t f = (uint64_t)blockIdx.x * BB_BLOCK + threadIdx.x;
-    if (f >= nframes) return;
     const uint64_t fn = (uint64_t)NTRACK * 2500;
     const uint64_t off = offsets ? (uint64_t)offsets[f] : (uint64_t)first_offset + f * fn;
     if (off + 160 * sizeof(word_t) > nbytes) { bad_tracks[f] = ~0ull >> (64 - NTRACK); return; }
@@ -203,6 +200,21 @@ void k_mark4_header_crc(const uint8_t *buf, uint64_t nbytes, const int64_t *offs
 #pragma unroll
     for (int k = 0; k < 12; ++k) bad |= r[k];
     bad_tracks[f] = (uint64_t)bad;
+}
+
+// One kernel for the three track counts (not a hot path: one thread per frame, 160 words):
+// `ntrack` picks the body in a wave-uniform switch.
+__global__ __launch_bounds__(BB_BLOCK)
+void k_mark4_header_crc(const uint8_t *buf, uint64_t nbytes, uint32_t ntrack, const int64_t *offsets,
+                        int64_t first_offset, uint64_t nframes, uint64_t *bad_tracks)
+{
+    const uint64_t f = (uint64_t)blockIdx.x * BB_BLOCK + threadIdx.x;
+    if (f >= nframes) return;
+    switch (ntrack) {
+    case 16: bb_m4_header_crc<16>(buf, nbytes, offsets, first_offset, f, bad_tracks); break;
+    case 32: bb_m4_header_crc<32>(buf, nbytes, offsets, first_offset, f, bad_tracks); break;
+    default: bb_m4_header_crc<64>(buf, nbytes, offsets, first_offset, f, bad_tracks); break;
+    }
 }
 
 struct bb_m4_args {

@@ -675,6 +675,60 @@ def repack_frames(dbuf, nframes, payload_in, bps, coder_in, chunk_in, nslot_in, 
     return out
 
 
+REQUANT_MAX_ROW_BITS = 256     # chunk * max(bps_in, bps_out) the requantize kernel takes
+REQUANT_MAX_SLOTS = 32         # ... and thread slots
+
+
+def requant_supported(bps_in, bps_out, chunk=1, nslot=1, payload_in=None, payload_out=None):
+    """Would `requant_frames` take these widths and this geometry?  (bb_requant_check; no device needed.)"""
+    if payload_in is None:
+        payload_in = _default_payload(bps_in, chunk)
+    if payload_out is None:
+        payload_out = _default_payload(bps_out, chunk)
+    return _lib.requant_check(bps_in, bps_out, chunk, nslot, payload_in, payload_out) == _lib.BB_OK
+
+
+def requant_table(coder_in, bps_in, coder_out, bps_out, scale=None):
+    """The table of `requant_frames` that is decode, times `scale`, encode: uint8 NumPy array
+    of ``1 << bps_in`` output codes by input code.  Made with the pieces the loop
+    ``fw.write(fr.read(n) * scale)`` runs on -- the decoder's float32 levels
+    (`_lib.get_levels`), a float32 product, the encode kernel (`encode_flat`) -- so it IS
+    that arithmetic.  ``scale=None`` stands for 1.0, which is exact."""
+    levels = _lib.get_levels(coder_in, bps_in).astype(np.float32)
+    if scale is not None:
+        if not np.isfinite(scale):
+            raise ValueError("requant_table: scale must be finite")
+        levels = levels * np.float32(scale)
+    levels = np.pad(levels, (0, max(0, 8 - levels.size)))       # (whole bytes at every width the encoder has)
+    packed = encode_flat(torch.from_numpy(levels).cuda(), coder_out, bps_out).cpu().numpy()
+    codes = (packed[:, None] >> np.arange(0, 8, bps_out, dtype=np.uint8)) & ((1 << bps_out) - 1)
+    return np.ascontiguousarray(codes.reshape(-1)[:1 << bps_in].astype(np.uint8))
+
+
+def requant_frames(dbuf, nframes, payload_in, bps_in, chunk, nslot, bps_out, payload_out, table, fill_code=0,
+                   src=None, src0=0, src_stride=0, row_lo=0, row_hi=None, first_row=0, out=None):
+    """Conversion between sample widths on the packed bytes (bb_requant_frames): rows
+    [row_lo, row_hi) of `nframes` input frame(set)s of `nslot` payloads with `chunk` codes of
+    `bps_in` bits per row, taken through the index `src` (-1 or an offset outside the buffer:
+    `fill_code`, not mapped) or at ``src0 + k * src_stride``, become output rows ``first_row +
+    (r - row_lo)`` of payloads of the same slot structure with codes of `bps_out` bits, code
+    c as ``table[c]`` -> uint8 device tensor of whole output frames, payload (F, s) at ``(F *
+    nslot + s) * payload_out``.  With `out` (such a tensor, contiguous) only the bytes of
+    the rows written change.  The row range and `first_row` are whole bytes of a slot stream
+    on both sides.  Nothing is decoded and nothing synchronises."""
+    if row_hi is None:
+        row_hi = _all_rows(nframes, payload_in, bps_in, chunk)
+    p = _lib.requant_params(bps_in, bps_out, chunk, nslot, payload_in, payload_out, table, fill_code,
+                            src0, src_stride, row_lo, row_hi, first_row)
+    if not _given(out, 'out', torch.uint8):
+        check(lib.bb_requant_check(C.byref(p)), 'bb_requant_frames')
+        nout = -(-(first_row + row_hi - row_lo) // (payload_out * 8 // bps_out // chunk))     # whole output frames
+        out = torch.empty(nout * nslot * payload_out, dtype=torch.uint8, device=dbuf.device)
+    check(lib.bb_requant_frames(_ptr(dbuf), dbuf.numel(), _ptr(src), nframes, C.byref(p),
+                                _ptr(out), out.numel(), _stream(dbuf)), 'bb_requant_frames')
+    return out
+
+
 TOUCH_MIN_BYTES = 16 << 20
 def _touch_max_bytes():
     try:                                # (as the library reads it: csrc/bbdecode.hip touch_mib_default)

@@ -785,6 +785,68 @@ int bb_repack_frames(const void *d_buf, size_t buf_nbytes,
                      void *d_out, size_t out_nbytes, void *stream);
 int bb_repack_check(const bb_repack_params *params);
 
+/*
+ * Conversion between sample widths on the packed bytes.  Decode, one float32
+ * gain and encode applied back to back (base/payload.py:314-330 with
+ * vdif/payload.py:25-114 and mark5b/payload.py:27-106; the loop of
+ * docs/tutorials/using_baseband.rst:536-593) are an exact function from input
+ * code to output code whatever the two widths are: a table of 1 << bps_in
+ * entries.  The caller supplies it (no coder appears here), so every pair of
+ * coders and every gain is the same call.
+ *
+ * Input exactly as for bb_repack_frames and bb_count_states: frame-slot (f, s)
+ * has its payload_in bytes at d_src[f * nslot + s] (-1, any negative offset or
+ * a payload not wholly inside the buffer: a source that counts nothing) or,
+ * with d_src == NULL, at src0 + (f * nslot + s) * src_stride (multiples of 4;
+ * the last payload inside the buffer, else BB_ERANGE).  Fields are taken LSB
+ * first; payloads may lie at any byte address; nothing outside the buffer is
+ * read.  nslot and chunk are the same on both sides, so a slot is one stream of
+ * codes: with R_in = payload_in * 8 / bps_in / chunk and R_out = payload_out *
+ * 8 / bps_out / chunk rows per frame, code p of counted row r in [row_lo,
+ * row_hi) of slot s has the output row G = first_row + (r - row_lo) and
+ *     field (G % R_out) * chunk + p of output payload (G / R_out, s) = map[c]
+ * or fill_code (not mapped) where the source counts nothing; payload (F, s)
+ * lies at (F * nslot + s) * payload_out.  Output bytes outside the rows written
+ * are not touched, so one request may be split over several calls into one
+ * output buffer.
+ *
+ * row_lo, row_hi and first_row must fall on a byte boundary of a slot stream on
+ * BOTH sides (times chunk * bps_in and times chunk * bps_out a multiple of 8),
+ * else BB_ENOTSUP: whole bytes only, there is no field-by-field edge.
+ * BB_ERANGE: row_hi > nframes * R_in, the last output row beyond out_nbytes,
+ * the last fixed-stride payload outside the buffer.  BB_EINVAL: NULL pointers,
+ * d_buf not 4-byte or d_out not 16-byte aligned, and what bb_requant_check
+ * answers with it.  Stream-ordered, never allocates, never synchronises;
+ * nframes == 0 or row_lo == row_hi launches nothing; an argument error leaves
+ * d_out untouched.
+ *
+ * bb_requant_check answers what the parameters alone decide (no buffers, no
+ * device): BB_EINVAL (a NULL block, reserved != 0, counts below 1, payloads
+ * that are 0, not multiples of 4 or not whole rows, row_lo > row_hi, fill_code
+ * or a used table entry outside [0, 1 << bps_out)), BB_ENOTSUP (a width not in
+ * {1, 2, 4, 8}, a chunk or slot count that is not a power of two, more than 32
+ * slots, chunk * max(bps_in, bps_out) > 256).  All 16 pairs of widths are BB_OK.
+ */
+typedef struct bb_requant_params {
+    int32_t  bps_in, bps_out;   /* 1, 2, 4, 8 each */
+    int32_t  chunk;             /* codes per (sample, slot), both sides; a power of two */
+    int32_t  nslot;             /* thread slots, both sides; a power of two */
+    int32_t  fill_code;         /* output code written where a source counts nothing */
+    int32_t  reserved;          /* 0 */
+    uint64_t payload_in;        /* bytes per frame and slot; multiples of 4; whole rows */
+    uint64_t payload_out;
+    int64_t  src0, src_stride;  /* used when d_src == NULL, as in bb_decode_frames */
+    uint64_t row_lo, row_hi;    /* rows [row_lo, row_hi) of the request's nframes * R_in */
+    uint64_t first_row;         /* output row of row_lo */
+    uint8_t  map[256];          /* output code by input code; entries >= 1 << bps_in are ignored */
+} bb_requant_params;
+
+int bb_requant_frames(const void *d_buf, size_t buf_nbytes,
+                      const int64_t *d_src, size_t nframes,
+                      const bb_requant_params *params,
+                      void *d_out, size_t out_nbytes, void *stream);
+int bb_requant_check(const bb_requant_params *params);
+
 /* ---- byte-aligned formats with an axis permutation --------------------- */
 
 /*
