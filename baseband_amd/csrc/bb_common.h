@@ -68,6 +68,10 @@ __device__ __forceinline__ uint64_t bb_perm(const bb_perm_t &p, uint64_t w)
 // (EOFError, base/payload.py:135-136).
 __device__ __forceinline__ bool bb_src_ok(int64_t so, uint64_t lim) { return (uint64_t)so < lim; }
 
+// The source offset of unit `u` (a frame, a frame-slot) of a kernel's arguments: from the index, else at the fixed stride.
+template <class A>
+__device__ __forceinline__ int64_t bb_src_at(const A &a, uint64_t u) { return a.src ? a.src[u] : a.src0 + (int64_t)u * a.src_stride; }
+
 // 16-byte store, optionally with the non-temporal hint (streamed output is
 // never re-read by this library).
 template <bool NT>

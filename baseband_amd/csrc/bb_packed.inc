@@ -1,0 +1,332 @@
+// The packed-byte entries of bbdecode.hip (bb_count_states, bb_count_states_bins, bb_repack_frames,
+// bb_requant_frames), their argument checks and what they share.  The ORDER of the checks is part of
+// the ABI: tests/golden/abi_return_codes.json holds it in place.
+extern "C++" { namespace {                                   // (the entries have C linkage: the include stands among them)
+// A slot's stream of rows: payloads of whole dwords that hold whole rows of `chunk` codes
+// of `bps` bits (both checked by the caller) -> *R rows in a payload.
+inline int slot_rows(uint64_t payload_nbytes, int bps, int chunk, uint64_t *R)
+{
+    if (payload_nbytes == 0 || (payload_nbytes & 3) || payload_nbytes > (1ull << 56)) return BB_EINVAL;
+    const uint64_t codes = payload_nbytes * 8 / (uint64_t)bps;
+    *R = codes / (uint64_t)chunk;
+    return codes % (uint64_t)chunk ? BB_EINVAL : BB_OK;
+}
+
+// Rows [row_lo, row_hi) of `nframes` frame(set)s of R rows each, row_lo <= row_hi (the parameter
+// checks); *nrows == 0: nothing is asked for, which is BB_OK whatever the buffers are.
+inline int rows_check(size_t nframes, uint64_t R, uint64_t row_lo, uint64_t row_hi, uint64_t *nrows)
+{
+    if ((nframes && R > (~0ull) / (uint64_t)nframes) || row_hi > (uint64_t)nframes * R) return BB_ERANGE;
+    *nrows = row_hi - row_lo;                                // (no frames: row_hi is 0)
+    return BB_OK;
+}
+
+// The source: `n` payloads of `span` bytes of the buffer, through the index or at the fixed
+// stride -> the source members of a kernel's arguments (every bb_*_args names them alike).
+template <class Args>
+inline int packed_source(Args &a, const void *d_buf, size_t buf_nbytes, const int64_t *d_src,
+                         int64_t src0, int64_t src_stride, uint64_t n, uint64_t span)
+{
+    if (!d_buf || ((uintptr_t)d_buf & 3)) return BB_EINVAL;
+    a.buf = (const uint8_t *)d_buf;
+    a.src = d_src;
+    a.src_lim = src_limit(buf_nbytes, span);
+    a.src0 = src0; a.src_stride = src_stride;
+    return d_src ? BB_OK : fixed_stride_check(src0, src_stride, 4, n, span, buf_nbytes);
+}
+
+// The output side of repack and requantize: rows [row_lo, row_hi) of the request become the
+// output rows from first_row on, R_out of them in each payload of payload_out bytes, nslot_out
+// payloads in a frame set; bi, bo: bits per row and slot, in and out.
+struct packed_out { uint64_t nrows, g_last, f_last; };       // rows asked for (rows_check), the last output row, its frame
+inline int packed_output(const void *d_out, size_t out_nbytes, size_t nframes, uint64_t payload_in, uint64_t R_in,
+                         uint64_t R_out, uint64_t payload_out, uint64_t nslot_out, uint64_t bi, uint64_t bo,
+                         uint64_t row_lo, uint64_t row_hi, uint64_t first_row, packed_out *o)
+{
+    if (!d_out || ((uintptr_t)d_out & 15)) return BB_EINVAL;
+    if (first_row > (1ull << 56)) return BB_ERANGE;
+    if ((((row_lo & 7) | (row_hi & 7) | (first_row & 7)) * (bi | bo)) & 7) return BB_ENOTSUP;   // whole bytes only (bi, bo are powers of two)
+    if (nframes && payload_in > (1ull << 58) / (uint64_t)nframes) return BB_ERANGE;
+    const int rc = rows_check(nframes, R_in, row_lo, row_hi, &o->nrows);
+    if (rc || !o->nrows) return rc;
+    o->g_last = first_row + (o->nrows - 1);                  // in slot nslot_out - 1
+    o->f_last = o->g_last / R_out;
+    if (o->f_last >= (1ull << 58) / (payload_out * nslot_out)) return BB_ERANGE;
+    const uint64_t end = (o->f_last * nslot_out + nslot_out - 1) * payload_out + ((o->g_last % R_out + 1) * bo + 7) / 8;
+    return end > out_nbytes ? BB_ERANGE : BB_OK;
+}
+
+// A payload as even pieces of at most `seg_max` bytes, multiples of 16 like seg_max -> their number, *seg_bytes of each.
+inline uint64_t even_pieces(uint64_t payload, uint64_t seg_max, uint32_t *seg_bytes)
+{
+    const uint64_t nseg = (payload + seg_max - 1) / seg_max;
+    *seg_bytes = (uint32_t)((((payload + nseg - 1) / nseg) + 15) & ~15ull);
+    return nseg;
+}
+
+// `fill_code` in every field of a dword; the grid of repack and requantize: a wave per work item
+inline uint32_t fill_word(int fill_code, int bps) { return (uint32_t)fill_code * (0xffffffffu / ((1u << bps) - 1u)); }
+#define BB_WAVE_ITEM_GRID 4096ull                    // workgroups: several rounds of what 256 CUs hold (repack: 4 each, 37 KiB of LDS)
+inline dim3 wave_grid(uint64_t nwork) { return capped_grid((nwork + BB_WAVES_PER_BLOCK - 1) / BB_WAVES_PER_BLOCK, BB_WAVE_ITEM_GRID); }
+} }
+
+// ---- sampler statistics (k_states.h).  EXTENSION: no reference counterpart. ----
+static int states_params_check(const bb_states_params *p, uint64_t *R)
+{
+    if (!p) return BB_EINVAL;
+    if (log2_bps(p->bps) < 0) return BB_ENOTSUP;
+    if (p->reserved != 0 || p->nslot < 1 || p->chunk < 1) return BB_EINVAL;
+    if (p->chunk & (p->chunk - 1)) return BB_ENOTSUP;
+    if ((int64_t)p->chunk * p->bps > 8 * (int64_t)BB_STATES_MAX_PHASES) return BB_ENOTSUP;   // the byte phases kept on chip
+    if (slot_rows(p->payload_nbytes, p->bps, p->chunk, R)) return BB_EINVAL;
+    if (p->row_lo > p->row_hi) return BB_EINVAL;
+    return BB_OK;
+}
+
+int bb_count_states_check(const bb_states_params *p) { uint64_t R; return states_params_check(p, &R); }
+
+#define BB_STATES_GRID 2048ull                       // workgroups: what 256 CUs hold at once; each flushes once
+#define BB_STATES_WAVE_ITEMS (1ull << 19)            // work items a wave may see: 2^31 bytes, its 32-bit counters cannot wrap
+
+int bb_count_states(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size_t nframes,
+                    const bb_states_params *p, unsigned long long *d_counts, size_t ncounts, void *stream)
+{
+    uint64_t R, nrows;
+    int rc = states_params_check(p, &R);
+    if (rc) return rc;
+    if (!d_counts || ((uintptr_t)d_counts & 7)) return BB_EINVAL;
+    const uint64_t nbins = ((uint64_t)p->nslot * (uint64_t)p->chunk) << p->bps;
+    if (ncounts < nbins) return BB_ERANGE;
+    rc = rows_check(nframes, R, p->row_lo, p->row_hi, &nrows);
+    if (rc || !nrows) return rc;
+    bb_states_args a;
+    rc = packed_source(a, d_buf, buf_nbytes, d_src, p->src0, p->src_stride,
+                       (uint64_t)nframes * (uint64_t)p->nslot, p->payload_nbytes);
+    if (rc) return rc;
+    a.counts = d_counts;
+    a.payload = p->payload_nbytes;
+    a.R = R;
+    a.row_lo = p->row_lo; a.row_hi = p->row_hi;
+    a.f_lo = p->row_lo / R;
+    const uint64_t nfr = (p->row_hi + R - 1) / R - a.f_lo;          // frames that hold a counted row
+    const uint64_t nseg = even_pieces(p->payload_nbytes, BB_STATES_SEG, &a.seg_bytes);
+    if (nseg > 0xffffffffull || nfr > (~0ull) / nseg) return BB_ERANGE;
+    a.nseg = (uint32_t)nseg;
+    a.nwork = nfr * nseg;
+    a.nslot = (uint32_t)p->nslot; a.chunk = (uint32_t)p->chunk;
+    a.bps = (uint32_t)p->bps; a.lbps = (uint32_t)log2_bps(p->bps);
+    const uint32_t cb = a.chunk * a.bps;
+    a.lphase = cb > 8 ? ceil_log2(cb / 8) : 0;
+    // workgroups per slot: one wave per work item up to what the device holds at once, and
+    // enough of them that no wave walks more than BB_STATES_WAVE_ITEMS
+    const int tb = g_tune_blocks.load();
+    const uint64_t cap = std::max<uint64_t>(1, (tb > 0 ? (uint64_t)tb : BB_STATES_GRID) / a.nslot);
+    uint64_t g = std::min<uint64_t>((a.nwork + BB_WAVES_PER_BLOCK - 1) / BB_WAVES_PER_BLOCK, cap);
+    const uint64_t need = (a.nwork + BB_WAVES_PER_BLOCK * BB_STATES_WAVE_ITEMS - 1) / (BB_WAVES_PER_BLOCK * BB_STATES_WAVE_ITEMS);
+    if (g < need) g = need;
+    if (g * a.nslot > BB_GRID_MAX) return BB_ERANGE;
+    const size_t lds = ((size_t)BB_WAVES_PER_BLOCK << (8 + a.lphase)) * 4 + (cb < 8 ? 64 : 0);
+    hipLaunchKernelGGL(k_count_states, dim3((unsigned)(g * a.nslot)), dim3(BB_BLOCK), lds, (hipStream_t)stream, a);
+    BB_HIP(hipGetLastError());
+    return BB_OK;
+}
+
+// ---- ... per time bin (k_state_bins.h) ----
+static int state_bins_params_check(const bb_states_params *p, uint64_t bin_rows, uint64_t *R)
+{
+    int rc = states_params_check(p, R);
+    if (rc) return rc;
+    if (bin_rows == 0 || bin_rows > 0x7fffffffull) return BB_EINVAL;          // a counter never exceeds bin_rows: int32 holds it
+    if ((bin_rows * (uint64_t)p->chunk * (uint64_t)p->bps) & 7) return BB_ENOTSUP;   // bins are whole bytes
+    if (((uint64_t)p->chunk << p->bps) > BB_BINS_MAX_PER_BIN) return BB_ENOTSUP;     // two bins fit a wave's window
+    return BB_OK;
+}
+
+int bb_count_states_bins_check(const bb_states_params *p, uint64_t bin_rows) { uint64_t R; return state_bins_params_check(p, bin_rows, &R); }
+
+#define BB_BINS_GRID 1280ull                         // workgroups: what 256 CUs hold at once with 32 KiB of LDS each
+
+int bb_count_states_bins(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size_t nframes,
+                         const bb_states_params *p, uint64_t bin_rows, uint64_t first_row, uint64_t nbins,
+                         uint32_t *d_counts, size_t ncounts, void *stream)
+{
+    uint64_t R, nrows;
+    int rc = state_bins_params_check(p, bin_rows, &R);
+    if (rc) return rc;
+    if (!d_counts || ((uintptr_t)d_counts & 3)) return BB_EINVAL;
+    const uint64_t cb = (uint64_t)p->chunk * (uint64_t)p->bps;                // bits per row, at most 128
+    if (first_row > (1ull << 56)) return BB_ERANGE;
+    if (((first_row * cb) | ((p->row_lo & 7) * cb) | ((p->row_hi & 7) * cb)) & 7) return BB_ENOTSUP;   // whole bytes only
+    const uint64_t nc = (uint64_t)p->chunk << p->bps;                         // counters per bin and slot
+    if (nbins > (~0ull) / (nc * (uint64_t)p->nslot) || ncounts < nbins * nc * (uint64_t)p->nslot) return BB_ERANGE;
+    if (nframes && p->payload_nbytes > (1ull << 62) / (uint64_t)nframes) return BB_ERANGE;
+    rc = rows_check(nframes, R, p->row_lo, p->row_hi, &nrows);
+    if (rc || !nrows) return rc;
+    if (nrows > (~0ull) - first_row) return BB_ERANGE;
+    if ((first_row + (nrows - 1)) / bin_rows >= nbins) return BB_ERANGE;   // the last counted row's bin
+    bb_state_bins_args a;
+    rc = packed_source(a, d_buf, buf_nbytes, d_src, p->src0, p->src_stride,
+                       (uint64_t)nframes * (uint64_t)p->nslot, p->payload_nbytes);
+    if (rc) return rc;
+    a.counts = d_counts;
+    a.payload = p->payload_nbytes;
+    // rows -> bytes of a slot's stream (R * cb / 8 = payload: a frame begins on a byte)
+    a.lo_byte = (p->row_lo / R) * a.payload + (p->row_lo % R) * cb / 8;
+    a.hi_byte = (p->row_hi / R) * a.payload + (p->row_hi % R) * cb / 8;
+    a.first_byte = first_row * cb / 8;
+    a.bin_bytes = bin_rows * cb / 8;
+    a.nbins = nbins;
+    a.f_lo = a.lo_byte / a.payload;
+    a.nfr = (a.hi_byte + a.payload - 1) / a.payload - a.f_lo;               // frames that hold a counted byte
+    a.nslot = (uint32_t)p->nslot; a.chunk = (uint32_t)p->chunk; a.bps = (uint32_t)p->bps;
+    a.lnc = (uint32_t)ceil_log2((uint32_t)nc);
+    a.win_bins = BB_BINS_WIN >> a.lnc;
+    // work items: even pieces of at most BB_STATES_SEG bytes that meet no more bins than a window holds
+    uint64_t seg_max = BB_STATES_SEG;
+    if (a.bin_bytes < seg_max && (a.win_bins - 1) * a.bin_bytes < seg_max) seg_max = (a.win_bins - 1) * a.bin_bytes;
+    a.nseg = (a.payload + seg_max - 1) / seg_max;                             // (bins of fewer than 16 bytes: pieces of seg_max)
+    a.seg_bytes = (uint32_t)seg_max;
+    if (seg_max >= 16) a.nseg = even_pieces(a.payload, seg_max & ~15ull, &a.seg_bytes);
+    if (a.nfr > (~0ull) / a.nseg || a.nfr * a.nseg > (~0ull) / a.nslot) return BB_ERANGE;
+    a.nwork = a.nfr * a.nseg * a.nslot;
+    // one contiguous run of items per wave, as many waves as the device holds at once
+    const uint64_t waves = std::min<uint64_t>(a.nwork, BB_BINS_GRID * BB_WAVES_PER_BLOCK);
+    a.per = (a.nwork + waves - 1) / waves;
+    const uint64_t runs = (a.nwork + a.per - 1) / a.per;
+    const uint64_t g = (runs + BB_WAVES_PER_BLOCK - 1) / BB_WAVES_PER_BLOCK;
+    hipLaunchKernelGGL(k_count_state_bins, dim3((unsigned)g), dim3(BB_BLOCK), 0, (hipStream_t)stream, a);
+    BB_HIP(hipGetLastError());
+    return BB_OK;
+}
+
+// ---- format conversion on the packed bytes (k_repack.h): decode and encode of
+//      base/payload.py:314-330, vdif/payload.py:25-114, mark5b/payload.py:27-106 back to back ----
+// The code map of a coder pair at `bps`: 0 identity, 1 invert every bit, 2 swap the two bits of a field; -1: none.
+static int repack_code_map(int coder_in, int coder_out, int bps)
+{
+    if (!coder_supported(coder_in, bps) || !coder_supported(coder_out, bps)) return -1;
+    if (coder_in == coder_out) return 0;
+    const bool vm = (coder_in == BB_CODER_VDIF && coder_out == BB_CODER_MARK5B) ||
+                    (coder_in == BB_CODER_MARK5B && coder_out == BB_CODER_VDIF);
+    if (vm && bps == 1) return 1;
+    if (vm && bps == 2) return 2;
+    return -1;                                              // VDIF <-> INT needs rescaling
+}
+
+static int repack_params_check(const bb_repack_params *p, uint64_t *R_in, uint64_t *R_out)
+{
+    if (!p) return BB_EINVAL;
+    if (log2_bps(p->bps) < 0) return BB_ENOTSUP;
+    if (p->reserved != 0 || p->chunk_in < 1 || p->nslot_in < 1 || p->chunk_out < 1 || p->nslot_out < 1) return BB_EINVAL;
+    if (repack_code_map(p->coder_in, p->coder_out, p->bps) < 0) return BB_ENOTSUP;
+    if ((p->chunk_in & (p->chunk_in - 1)) || (p->nslot_in & (p->nslot_in - 1)) ||
+        (p->chunk_out & (p->chunk_out - 1)) || (p->nslot_out & (p->nslot_out - 1))) return BB_ENOTSUP;
+    if ((int64_t)p->nslot_in * p->chunk_in != (int64_t)p->nslot_out * p->chunk_out) return BB_EINVAL;
+    if ((uint32_t)p->nslot_in > BB_REPACK_MAX_SLOTS || (uint32_t)p->nslot_out > BB_REPACK_MAX_SLOTS) return BB_ENOTSUP;
+    if ((int64_t)p->nslot_in * p->chunk_in * p->bps > (int64_t)BB_REPACK_MAX_ROW_BITS) return BB_ENOTSUP;
+    if (slot_rows(p->payload_in, p->bps, p->chunk_in, R_in) ||
+        slot_rows(p->payload_out, p->bps, p->chunk_out, R_out)) return BB_EINVAL;
+    if (p->fill_code < 0 || p->fill_code >= (1 << p->bps)) return BB_EINVAL;
+    if (p->row_lo > p->row_hi) return BB_EINVAL;
+    return BB_OK;
+}
+
+int bb_repack_check(const bb_repack_params *p) { uint64_t R_in, R_out; return repack_params_check(p, &R_in, &R_out); }
+
+int bb_repack_frames(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size_t nframes,
+                     const bb_repack_params *p, void *d_out, size_t out_nbytes, void *stream)
+{
+    uint64_t R_in, R_out; packed_out o;
+    int rc = repack_params_check(p, &R_in, &R_out);
+    if (rc) return rc;
+    const uint64_t bi = (uint64_t)p->chunk_in * (uint64_t)p->bps, bo = (uint64_t)p->chunk_out * (uint64_t)p->bps;   // bits per row and slot
+    rc = packed_output(d_out, out_nbytes, nframes, p->payload_in, R_in, R_out, p->payload_out, (uint64_t)p->nslot_out, bi, bo,
+                       p->row_lo, p->row_hi, p->first_row, &o);
+    if (rc || !o.nrows) return rc;
+    bb_repack_args a;
+    rc = packed_source(a, d_buf, buf_nbytes, d_src, p->src0, p->src_stride,
+                       (uint64_t)nframes * (uint64_t)p->nslot_in, p->payload_in);
+    if (rc) return rc;
+    a.out = (uint8_t *)d_out;
+    a.buf_n = buf_nbytes;
+    a.pay_in = p->payload_in; a.pay_out = p->payload_out;
+    a.row_lo = p->row_lo; a.first_row = p->first_row; a.nrows = o.nrows;
+    a.R_out = R_out;
+    a.F0 = p->first_row / R_out;
+    a.nslot_in = (uint32_t)p->nslot_in; a.nslot_out = (uint32_t)p->nslot_out;
+    a.lbi = ceil_log2(bi); a.lbo = ceil_log2(bo);
+    a.T = BB_REPACK_ITEM_BITS / (uint32_t)(bi * a.nslot_in);                  // at least 256 rows: 16 bytes or more of every slot
+    a.sstride = ((a.T << a.lbi) >> 3) + BB_REPACK_SLACK;
+    a.nseg = (R_out + a.T - 1) / a.T;
+    const uint64_t nf = o.f_last - a.F0 + 1;
+    if (nf > (~0ull) / a.nseg) return BB_ERANGE;
+    a.nwork = nf * a.nseg;
+    a.map = (uint32_t)repack_code_map(p->coder_in, p->coder_out, p->bps);
+    a.fillw = fill_word(p->fill_code, p->bps);
+    // chunks of min(bi, bo) bits stay together; equal slot structures are a stream of whole dwords
+    a.lg = a.lbi == a.lbo ? 5u : std::min(5u, std::min(a.lbi, a.lbo));
+    const dim3 grid = wave_grid(a.nwork);
+    hipLaunchKernelGGL(k_repack, grid, dim3(BB_BLOCK), 0, (hipStream_t)stream, a);
+    BB_HIP(hipGetLastError());
+    return BB_OK;
+}
+
+// ---- conversion between sample widths on the packed bytes (k_requant.h): decode, one gain and
+//      encode of base/payload.py:314-330, vdif/payload.py:25-114, mark5b/payload.py:27-106 as a table ----
+static int requant_params_check(const bb_requant_params *p, uint64_t *R_in, uint64_t *R_out)
+{
+    if (!p) return BB_EINVAL;
+    if (log2_bps(p->bps_in) < 0 || log2_bps(p->bps_out) < 0) return BB_ENOTSUP;
+    if (p->reserved != 0 || p->chunk < 1 || p->nslot < 1) return BB_EINVAL;
+    if ((p->chunk & (p->chunk - 1)) || (p->nslot & (p->nslot - 1))) return BB_ENOTSUP;
+    if ((uint32_t)p->nslot > BB_REQUANT_MAX_SLOTS) return BB_ENOTSUP;
+    if ((int64_t)p->chunk * std::max(p->bps_in, p->bps_out) > (int64_t)BB_REQUANT_MAX_ROW_BITS) return BB_ENOTSUP;
+    if (slot_rows(p->payload_in, p->bps_in, p->chunk, R_in) ||
+        slot_rows(p->payload_out, p->bps_out, p->chunk, R_out)) return BB_EINVAL;
+    if (p->fill_code < 0 || p->fill_code >= (1 << p->bps_out)) return BB_EINVAL;
+    for (int c = 0; c < (1 << p->bps_in); ++c)
+        if ((int)p->map[c] >= (1 << p->bps_out)) return BB_EINVAL;
+    if (p->row_lo > p->row_hi) return BB_EINVAL;
+    return BB_OK;
+}
+
+int bb_requant_check(const bb_requant_params *p) { uint64_t R_in, R_out; return requant_params_check(p, &R_in, &R_out); }
+
+int bb_requant_frames(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size_t nframes,
+                      const bb_requant_params *p, void *d_out, size_t out_nbytes, void *stream)
+{
+    uint64_t R_in, R_out; packed_out o;
+    int rc = requant_params_check(p, &R_in, &R_out);
+    if (rc) return rc;
+    const uint64_t bi = (uint64_t)p->chunk * (uint64_t)p->bps_in, bo = (uint64_t)p->chunk * (uint64_t)p->bps_out;   // bits per row and slot
+    rc = packed_output(d_out, out_nbytes, nframes, p->payload_in, R_in, R_out, p->payload_out, (uint64_t)p->nslot, bi, bo,
+                       p->row_lo, p->row_hi, p->first_row, &o);
+    if (rc || !o.nrows) return rc;
+    bb_requant_args a;
+    rc = packed_source(a, d_buf, buf_nbytes, d_src, p->src0, p->src_stride,
+                       (uint64_t)nframes * (uint64_t)p->nslot, p->payload_in);
+    if (rc) return rc;
+    a.out = (uint8_t *)d_out;
+    a.buf_n = buf_nbytes;
+    a.pay_in = p->payload_in; a.pay_out = p->payload_out;
+    // rows -> bytes of a slot's output stream and bits of its input stream (R * bo / 8 = payload_out: a frame begins on a byte)
+    a.ya = (p->first_row / R_out) * a.pay_out + (p->first_row % R_out) * bo / 8;
+    a.yb = a.ya + ((o.nrows / 8) * bo + (o.nrows % 8) * bo / 8);
+    a.xbit_a = p->row_lo * bi;
+    a.F0 = p->first_row / R_out;
+    a.nslot = (uint32_t)p->nslot;
+    a.lbi = (uint32_t)log2_bps(p->bps_in); a.lbo = (uint32_t)log2_bps(p->bps_out);
+    a.seg = a.lbi > a.lbo ? BB_REQUANT_ITEM_BYTES >> (a.lbi - a.lbo) : BB_REQUANT_ITEM_BYTES;
+    a.nseg = (a.pay_out + a.seg - 1) / a.seg;
+    const uint64_t nf = o.f_last - a.F0 + 1;
+    if (nf > (~0ull) / (a.nseg * a.nslot)) return BB_ERANGE;
+    a.nwork = nf * a.nseg * a.nslot;
+    a.fillw = fill_word(p->fill_code, p->bps_out);
+    uint8_t *m = reinterpret_cast<uint8_t *>(a.map);                          // (entries the input cannot have: 0)
+    for (int c = 0; c < 256; ++c) m[c] = c < (1 << p->bps_in) ? p->map[c] : 0;
+    const dim3 grid = wave_grid(a.nwork);
+    hipLaunchKernelGGL(k_requant, grid, dim3(BB_BLOCK), 0, (hipStream_t)stream, a);
+    BB_HIP(hipGetLastError());
+    return BB_OK;
+}
+

@@ -89,7 +89,7 @@ void k_decode_flat_burst(bb_burst_args a)
         if ((uint32_t)lane < np) {
             const uint64_t w = w0 + (uint32_t)lane;
             const uint64_t fs = a.nseg == 1 ? w : w / a.nseg;
-            so_l = a.src ? a.src[fs] : a.src0 + (int64_t)fs * a.src_stride;
+            so_l = bb_src_at(a, fs);
         }
         for (uint32_t q = 0; q < np; ++q) {
             const uint32_t lo32 = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(so_l & 0xffffffff), q);

@@ -53,7 +53,7 @@ void k_decode_flat_pipe(bb_flat_args a)
         uint64_t fs, seg;
         if (a.nseg == 1) { fs = work; seg = 0; }
         else { fs = work / a.nseg; seg = work - fs * a.nseg; }
-        const int64_t so = a.src ? a.src[fs] : a.src0 + (int64_t)fs * a.src_stride;
+        const int64_t so = bb_src_at(a, fs);
         valid = bb_src_ok(so, a.src_lim);
         const uint32_t *in = reinterpret_cast<const uint32_t *>(a.buf + (valid ? so : 0));
         const uint64_t tile0 = seg * a.seg_tiles + (uint64_t)wave * a.tpw;
@@ -181,7 +181,7 @@ void k_decode_flat_aln(bb_flat_args a)
         uint64_t fs, seg;
         if (a.nseg == 1) { fs = work; seg = 0; }
         else { fs = work / a.nseg; seg = work - fs * a.nseg; }
-        const int64_t so = a.src ? a.src[fs] : a.src0 + (int64_t)fs * a.src_stride;
+        const int64_t so = bb_src_at(a, fs);
         valid = bb_src_ok(so, a.src_lim);
         // absolute dword index of the payload start in the buffer; its low six
         // bits are the misalignment against 256-byte blocks
@@ -303,7 +303,7 @@ void k_decode_flat_span(bb_flat_args a)
 
     auto offset_of = [&](uint64_t frame) -> int64_t {
         if (frame >= a.nfs) return -1;
-        return a.src ? a.src[frame] : a.src0 + (int64_t)frame * a.src_stride;
+        return bb_src_at(a, frame);
     };
 
     struct span { uint64_t boundary; bool okA, okB; };   // wave-uniform
@@ -383,7 +383,7 @@ void k_decode_flat2_bytes(bb_flat_args a)
         ? bb_f4{a.fill_re, a.fill_im, a.fill_re, a.fill_im}
         : bb_f4{a.fill_re, a.fill_re, a.fill_re, a.fill_re};
     for (uint64_t fs = blockIdx.x; fs < a.nfs; fs += gridDim.x) {
-        const int64_t so = a.src ? a.src[fs] : a.src0 + (int64_t)fs * a.src_stride;
+        const int64_t so = bb_src_at(a, fs);
         const bool valid = bb_src_ok(so, a.src_lim);
         const uint8_t *in = a.buf + (valid ? so : 0);
         float *obase = a.out + fs * E;

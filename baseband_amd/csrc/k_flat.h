@@ -132,7 +132,7 @@ void k_decode_flat(bb_flat_args a)
         uint64_t fs, seg;
         if (a.nseg == 1) { fs = work; seg = 0; }
         else { fs = work / a.nseg; seg = work - fs * a.nseg; }
-        const int64_t so = a.src ? a.src[fs] : a.src0 + (int64_t)fs * a.src_stride;
+        const int64_t so = bb_src_at(a, fs);
         const bool valid = bb_src_ok(so, a.src_lim);
         const uint32_t *in = reinterpret_cast<const uint32_t *>(a.buf + (valid ? so : 0));
 

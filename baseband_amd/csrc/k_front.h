@@ -75,7 +75,7 @@ void k_decode_flat_front(bb_flat_args a, bb_front_geom g)
     uint32_t cur_s = 0, nxt_s = 0;
 
     auto issue = [&](uint64_t f, uint32_t jj, uint32_t (&w)[TPW + 1], bool &valid, uint32_t &s) {
-        const int64_t so = a.src ? a.src[f] : a.src0 + (int64_t)f * a.src_stride;
+        const int64_t so = bb_src_at(a, f);
         valid = so >= 0;
         const uint8_t *p = a.buf + (valid ? so : 0);
         // misalignment of the payload against 256-byte blocks of the address
@@ -191,7 +191,7 @@ void k_decode_flat_es(bb_flat_args a, uint64_t ntile_total, uint64_t per_stripe)
         if (t < ntile_total) {                              // wave-uniform
             const uint64_t fs = t / ntiles;
             const uint32_t tile = (uint32_t)(t - fs * ntiles);
-            const int64_t so = a.src ? a.src[fs] : a.src0 + (int64_t)fs * a.src_stride;
+            const int64_t so = bb_src_at(a, fs);
             fsv[u] = fs; tilev[u] = tile; validv[u] = so >= 0;
             const uint64_t dw = (uint64_t)tile * 64 + lane;
             if (so >= 0 && dw < a.ndw)
@@ -270,7 +270,7 @@ void k_decode_flat_elem(bb_flat_args a, uint64_t fps)
 #pragma unroll
     for (int k = 0; k < BB_ELEM_STRIPES; ++k) {
         const uint64_t f = (uint64_t)k * fps + fl;
-        sov[k] = f < a.nfs ? (a.src ? a.src[f] : a.src0 + (int64_t)f * a.src_stride) : -2;
+        sov[k] = f < a.nfs ? bb_src_at(a, f) : -2;
     }
 #pragma unroll
     for (int k = 0; k < BB_ELEM_STRIPES; ++k) {

@@ -130,7 +130,7 @@ void k_decode_half_flat(bb_half_args a)
         uint64_t fs, seg;
         if (a.nseg == 1) { fs = work; seg = 0; }
         else { fs = work / a.nseg; seg = work - fs * a.nseg; }
-        const int64_t so = a.src ? a.src[fs] : a.src0 + (int64_t)fs * a.src_stride;
+        const int64_t so = bb_src_at(a, fs);
         const bool valid = bb_src_ok(so, a.src_lim);
         const uint64_t tile0 = seg * a.seg_tiles + (uint64_t)wave * a.tpw;
         const uint64_t seg_b_end = (seg + 1) * a.seg_tiles * 256 < pbytes ? (seg + 1) * a.seg_tiles * 256 : pbytes;
@@ -216,7 +216,7 @@ void k_decode_half_rows(bb_half_args a)
         __syncthreads();                          // the table is built / the last item has been written
         for (uint32_t sl = threadIdx.x; sl < nslot; sl += BB_BLOCK) {
             const uint64_t fs = f * nslot + sl;
-            const int64_t so = a.src ? a.src[fs] : a.src0 + (int64_t)fs * a.src_stride;
+            const int64_t so = bb_src_at(a, fs);
             s_so[sl] = bb_src_ok(so, a.src_lim) ? so : -1;
         }
         __syncthreads();

@@ -71,7 +71,7 @@ void k_decode_flat_lut(bb_flat_args a)
         uint64_t fs, seg;
         if (a.nseg == 1) { fs = work; seg = 0; }
         else { fs = work / a.nseg; seg = work - fs * a.nseg; }
-        const int64_t so = a.src ? a.src[fs] : a.src0 + (int64_t)fs * a.src_stride;
+        const int64_t so = bb_src_at(a, fs);
         valid = bb_src_ok(so, a.src_lim);
         const uint8_t *pp = a.buf + (valid ? (uint64_t)so : 0);
         const uintptr_t b0 = reinterpret_cast<uintptr_t>(pp);

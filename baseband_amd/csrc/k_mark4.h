@@ -275,7 +275,7 @@ void k_decode_mark4(bb_m4_args a)
         uint64_t f, seg;
         if (a.nseg == 1) { f = work; seg = 0; }
         else { f = work / a.nseg; seg = work - f * a.nseg; }
-        const int64_t so = a.src ? a.src[f] : a.src0 + (int64_t)f * a.src_stride;
+        const int64_t so = bb_src_at(a, f);
         valid = bb_src_ok(so, a.src_lim);
         const word_t *in = reinterpret_cast<const word_t *>(a.buf + (valid ? so : 0));
         const uint64_t tile0 = seg * a.seg_tiles + (uint64_t)wave * a.tpw;
@@ -385,7 +385,7 @@ void k_decode_mark4_lds(bb_m4_args a)
         uint64_t f, seg;
         if (a.nseg == 1) { f = work; seg = 0; }
         else { f = work / a.nseg; seg = work - f * a.nseg; }
-        const int64_t so = a.src ? a.src[f] : a.src0 + (int64_t)f * a.src_stride;
+        const int64_t so = bb_src_at(a, f);
         const bool valid = bb_src_ok(so, a.src_lim);
         const uint64_t tile0 = seg * a.seg_tiles + (uint64_t)wave * a.tpw;
         const uint64_t w_end = (seg + 1) * a.seg_tiles * 64 < a.nwords ? (seg + 1) * a.seg_tiles * 64 : a.nwords;
@@ -499,7 +499,7 @@ void k_decode_mark4_select(bb_m4_args a, uint32_t nout)
         uint64_t f, seg;
         if (a.nseg == 1) { f = pwork; seg = 0; }
         else { f = pwork / a.nseg; seg = pwork - f * a.nseg; }
-        const int64_t so = a.src ? a.src[f] : a.src0 + (int64_t)f * a.src_stride;
+        const int64_t so = bb_src_at(a, f);
         const bool valid = bb_src_ok(so, a.src_lim);
         float *obase = a.out + f * E;
         const uint64_t tile0 = seg * a.seg_tiles + (uint64_t)wave * a.tpw;

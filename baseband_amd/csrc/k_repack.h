@@ -86,7 +86,7 @@ __device__ __forceinline__ uint32_t bb_repack_in_byte(const bb_repack_args &a, u
 {
     const uint64_t f = x / a.pay_in;
     const uint64_t fs = f * a.nslot_in + s;
-    const int64_t so = a.src ? a.src[fs] : a.src0 + (int64_t)fs * a.src_stride;
+    const int64_t so = bb_src_at(a, fs);
     if (!bb_src_ok(so, a.src_lim)) return a.fillw & 0xffu;
     return bb_repack_map(a.buf[(uint64_t)so + (x - f * a.pay_in)], a.map) & 0xffu;
 }
@@ -228,7 +228,7 @@ void k_repack(bb_repack_args a)
                 bool fast = x0 >= ia && x0 + 16u <= ib && off + 16u <= a.pay_in;
                 if (fast) {
                     const uint64_t fs = f * a.nslot_in + s;
-                    const int64_t so = a.src ? a.src[fs] : a.src0 + (int64_t)fs * a.src_stride;
+                    const int64_t so = bb_src_at(a, fs);
                     bb_u4 v;
                     if (!bb_src_ok(so, a.src_lim)) {
                         v = bb_u4{a.fillw, a.fillw, a.fillw, a.fillw};

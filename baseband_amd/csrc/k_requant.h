@@ -152,7 +152,7 @@ __device__ __forceinline__ void bb_requant_item(const bb_requant_args &a, const 
                 bool done = false;
                 if (off + (uint32_t)NIN <= paybits) {
                     const uint64_t fs = f * a.nslot + s;
-                    const int64_t so = a.src ? a.src[fs] : a.src0 + (int64_t)fs * a.src_stride;
+                    const int64_t so = bb_src_at(a, fs);
                     if (!bb_src_ok(so, a.src_lim)) {
                         o[0] = o[1] = o[2] = o[3] = a.fillw;
                         done = true;

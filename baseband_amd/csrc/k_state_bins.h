@@ -218,7 +218,7 @@ void k_count_state_bins(bb_state_bins_args a)
         const uint64_t seg = seg_next;
         if (++seg_next == a.nseg) { seg_next = 0; if (++fr == a.nfr) { fr = 0; ++slot_next; } }   // (the item after this one)
         const uint64_t fs = f * a.nslot + slot;
-        const int64_t so = a.src ? a.src[fs] : a.src0 + (int64_t)fs * a.src_stride;
+        const int64_t so = bb_src_at(a, fs);
         if (!bb_src_ok(so, a.src_lim)) continue;             // missing, invalid or outside the buffer: counts nothing
         // bytes [q0, q1) of this frame-slot
         const uint64_t fbyte = f * a.payload;
@@ -243,37 +243,25 @@ void k_count_state_bins(bb_state_bins_args a)
 
         const uint8_t *p0 = a.buf + (uint64_t)so + q0;
         const uint32_t qlow = (uint32_t)q0;
-        const uint32_t mis = (uint32_t)reinterpret_cast<uintptr_t>(p0) & 15u;
-        uint32_t nhead = mis ? 16u - mis : 0u;
-        if (nhead > n) nhead = n;
-        const uint32_t nmid = (n - nhead) >> 4;              // 16-byte pieces, aligned
-        const uint32_t ntail = n - nhead - (nmid << 4);
-        const bb_u4 *pmid = reinterpret_cast<const bb_u4 *>(p0 + nhead);
+        const bb_pieces x = bb_pieces_split(p0, n);
+        const bb_u4 *pmid = reinterpret_cast<const bb_u4 *>(p0 + x.nhead);
         bb_u4 v[BB_STATES_NL];
 #pragma unroll
-        for (int k = 0; k < BB_STATES_NL; ++k) {
-            const uint32_t c = (uint32_t)k * BB_WAVE + (uint32_t)lane;
-            v[k] = bb_u4{0u, 0u, 0u, 0u};
-            if (c < nmid) v[k] = pmid[c];
-        }
-        {
-            // the bytes around the aligned middle, one per lane
-            const uint32_t t = (uint32_t)lane & 31u;
-            const uint32_t off = lane < 32 ? t : nhead + (nmid << 4) + t;
-            if (t < (lane < 32 ? nhead : ntail)) {
-                uint32_t lb, left;
-                bb_bins_at(off, left0, bbc, lb, left);
-                bb_bins_add_byte(win, p0[off], qlow + off, lbase + lb, a.bps, lbps, cm, lnc, 1u);
-            }
+        for (int k = 0; k < BB_STATES_NL; ++k) bb_piece_load(v[k], pmid, x.nmid, (uint32_t)k * BB_WAVE + (uint32_t)lane);
+        uint32_t off;
+        if (bb_pieces_edge_byte(x, lane, off)) {
+            uint32_t lb, left;
+            bb_bins_at(off, left0, bbc, lb, left);
+            bb_bins_add_byte(win, p0[off], qlow + off, lbase + lb, a.bps, lbps, cm, lnc, 1u);
         }
 #pragma unroll
         for (int k = 0; k < BB_STATES_NL; ++k) {
             const uint32_t k0 = (uint32_t)k * BB_WAVE;
-            if (k0 >= nmid) break;
-            const uint32_t W = (uint32_t)__builtin_amdgcn_readfirstlane((int)v[k].x);     // (lane 0 holds a piece: k0 < nmid)
-            const uint32_t nv = nmid - k0 < BB_WAVE ? nmid - k0 : BB_WAVE;                // pieces of this load
-            const uint32_t ta = nhead + (k0 << 4);                                        // its first byte
-            if (bbc >= 64u && __all((uint32_t)lane >= nv || (v[k].x == W && v[k].y == W && v[k].z == W && v[k].w == W))) {
+            if (k0 >= x.nmid) break;
+            const uint32_t W = (uint32_t)__builtin_amdgcn_readfirstlane((int)v[k].x);     // (lane 0 holds a piece: k0 < x.nmid)
+            const uint32_t nv = x.nmid - k0 < BB_WAVE ? x.nmid - k0 : BB_WAVE;            // pieces of this load
+            const uint32_t ta = x.nhead + (k0 << 4);                                        // its first byte
+            if (bbc >= 64u && __all((uint32_t)lane >= nv || bb_piece_repeats(v[k], W))) {
                 // nv pieces that repeat one dword: bin after bin, lane o < 16 adds the bytes at ta + o + 16 m
                 const uint32_t tb = ta + (nv << 4);
                 uint32_t lb, left;
@@ -290,7 +278,7 @@ void k_count_state_bins(bb_state_bins_args a)
                     t = e;
                     left = bbc;
                 }
-            } else if (k0 + (uint32_t)lane < nmid) {
+            } else if (k0 + (uint32_t)lane < x.nmid) {
                 const uint32_t t0 = ta + ((uint32_t)lane << 4);
                 uint32_t lb, left;
                 bb_bins_at(t0, left0, bbc, lb, left);

@@ -63,6 +63,37 @@ __device__ __forceinline__ void bb_states_add16(uint32_t *hist, const bb_u4 &v, 
     }
 }
 
+// ---- a work item's bytes [p0, p0 + n) as this kernel and k_count_state_bins walk them (above).  The helpers
+// are cut where both kernels keep the instructions of the text written out (tools/check_isa.py --against) ----
+struct bb_pieces { uint32_t nhead, nmid, ntail; };           // bytes in front, 16-byte pieces, bytes behind
+
+__device__ __forceinline__ bb_pieces bb_pieces_split(const uint8_t *p0, uint32_t n)
+{
+    const uint32_t mis = (uint32_t)reinterpret_cast<uintptr_t>(p0) & 15u;
+    uint32_t nhead = mis ? 16u - mis : 0u;
+    if (nhead > n) nhead = n;
+    const uint32_t nmid = (n - nhead) >> 4;
+    return bb_pieces{nhead, nmid, n - nhead - (nmid << 4)};
+}
+
+// Piece c of the middle, zero past the last.  A lane loads its BB_STATES_NL pieces k * BB_WAVE + lane before the first add.
+__device__ __forceinline__ void bb_piece_load(bb_u4 &v, const bb_u4 *pmid, uint32_t nmid, uint32_t c)
+{
+    v = bb_u4{0u, 0u, 0u, 0u};
+    if (c < nmid) v = pmid[c];
+}
+
+// The bytes around the middle, one per lane: lanes 0-31 the head, 32-63 the tail -> this lane has p0[off].
+__device__ __forceinline__ bool bb_pieces_edge_byte(bb_pieces x, int lane, uint32_t &off)
+{
+    const uint32_t t = (uint32_t)lane & 31u;
+    off = lane < 32 ? t : x.nhead + (x.nmid << 4) + t;
+    return t < (lane < 32 ? x.nhead : x.ntail);
+}
+
+// A piece repeats the dword W; a wave load does when __all of its lanes that hold a piece say so.
+__device__ __forceinline__ bool bb_piece_repeats(const bb_u4 &v, uint32_t W) { return v.x == W && v.y == W && v.z == W && v.w == W; }
+
 __global__ __launch_bounds__(BB_BLOCK)
 void k_count_states(bb_states_args a)
 {
@@ -85,7 +116,7 @@ void k_count_states(bb_states_args a)
         const uint32_t seg = (uint32_t)(w - fr * a.nseg);
         const uint64_t f = a.f_lo + fr;
         const uint64_t fs = f * a.nslot + slot;
-        const int64_t so = a.src ? a.src[fs] : a.src0 + (int64_t)fs * a.src_stride;
+        const int64_t so = bb_src_at(a, fs);
         if (!bb_src_ok(so, a.src_lim)) continue;             // missing, invalid or outside the buffer: counts nothing
         // the bits of this frame-slot that count
         const uint64_t g0 = f * a.R;
@@ -113,43 +144,31 @@ void k_count_states(bb_states_args a)
         if (q0 >= q1) continue;
         const uint32_t n = (uint32_t)(q1 - q0);
         const uint8_t *p0 = pay + q0;
-        const uint32_t mis = (uint32_t)reinterpret_cast<uintptr_t>(p0) & 15u;
-        uint32_t nhead = mis ? 16u - mis : 0u;
-        if (nhead > n) nhead = n;
-        const uint32_t nmid = (n - nhead) >> 4;              // 16-byte pieces, aligned
-        const uint32_t ntail = n - nhead - (nmid << 4);
-        const bb_u4 *pmid = reinterpret_cast<const bb_u4 *>(p0 + nhead);
+        const bb_pieces x = bb_pieces_split(p0, n);
+        const bb_u4 *pmid = reinterpret_cast<const bb_u4 *>(p0 + x.nhead);
         bb_u4 v[BB_STATES_NL];
 #pragma unroll
-        for (int k = 0; k < BB_STATES_NL; ++k) {
-            const uint32_t c = (uint32_t)k * BB_WAVE + (uint32_t)lane;
-            v[k] = bb_u4{0u, 0u, 0u, 0u};
-            if (c < nmid) v[k] = pmid[c];
+        for (int k = 0; k < BB_STATES_NL; ++k) bb_piece_load(v[k], pmid, x.nmid, (uint32_t)k * BB_WAVE + (uint32_t)lane);
+        uint32_t off;
+        if (bb_pieces_edge_byte(x, lane, off)) {
+            const uint32_t b = p0[off];
+            atomicAdd(&hist[(b << lP) + (((uint32_t)q0 + off) & pm)], 1u);
         }
-        {
-            // the bytes around the aligned middle, one per lane
-            const uint32_t t = (uint32_t)lane & 31u;
-            const uint32_t off = lane < 32 ? t : nhead + (nmid << 4) + t;
-            if (t < (lane < 32 ? nhead : ntail)) {
-                const uint32_t b = p0[off];
-                atomicAdd(&hist[(b << lP) + (((uint32_t)q0 + off) & pm)], 1u);
-            }
-        }
-        const uint32_t phA = ((uint32_t)q0 + nhead) & pm;     // phase of a piece's first byte: pieces are 16 bytes apart, P divides 16
+        const uint32_t phA = ((uint32_t)q0 + x.nhead) & pm;     // phase of a piece's first byte: pieces are 16 bytes apart, P divides 16
 #pragma unroll
         for (int k = 0; k < BB_STATES_NL; ++k) {
             const uint32_t k0 = (uint32_t)k * BB_WAVE;
-            if (k0 >= nmid) break;
-            const uint32_t W = (uint32_t)__builtin_amdgcn_readfirstlane((int)v[k].x);     // (lane 0 holds a piece: k0 < nmid)
-            const uint32_t nv = nmid - k0 < BB_WAVE ? nmid - k0 : BB_WAVE;                // pieces of this load
-            if (__all((uint32_t)lane >= nv || (v[k].x == W && v[k].y == W && v[k].z == W && v[k].w == W))) {
+            if (k0 >= x.nmid) break;
+            const uint32_t W = (uint32_t)__builtin_amdgcn_readfirstlane((int)v[k].x);     // (lane 0 holds a piece: k0 < x.nmid)
+            const uint32_t nv = x.nmid - k0 < BB_WAVE ? x.nmid - k0 : BB_WAVE;            // pieces of this load
+            if (__all((uint32_t)lane >= nv || bb_piece_repeats(v[k], W))) {
                 // nv pieces that repeat one dword: byte j of it 4 * nv times, dealt evenly over the phases it meets
                 const uint32_t Q = lP > 2 ? 1u << (lP - 2) : 1u;
                 if ((uint32_t)lane < 4u * Q) {
                     const uint32_t j = (uint32_t)lane & 3u, m = (uint32_t)lane >> 2;
                     atomicAdd(&hist[(((W >> (8 * j)) & 0xffu) << lP) + ((phA + 4u * m + j) & pm)], 4u * nv / Q);
                 }
-            } else if (k0 + (uint32_t)lane < nmid) {
+            } else if (k0 + (uint32_t)lane < x.nmid) {
                 bb_states_add16(hist, v[k], lP, pm, phA);
             }
         }

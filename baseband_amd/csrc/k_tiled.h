@@ -67,7 +67,7 @@ void k_decode_i8_tiled(bb_tiled_args a)
         const uint32_t nt_tile = (uint32_t)((a.t_hi - t0 < tt) ? a.t_hi - t0 : tt);
         const uint32_t c0 = ci * tc;
         const uint32_t nc_tile = (a.nchan - c0 < tc) ? a.nchan - c0 : tc;
-        const int64_t so = a.src ? a.src[f] : a.src0 + (int64_t)f * a.src_stride;
+        const int64_t so = bb_src_at(a, f);
         const bool valid = bb_src_ok(so, a.src_lim);
         const uint16_t *in = reinterpret_cast<const uint16_t *>(a.buf + (valid ? so : 0));
 
@@ -204,7 +204,7 @@ void k_decode_i8_stage(bb_tiled_args a)
         const uint32_t nt_tile = (uint32_t)((a.t_hi - t0 < tt) ? a.t_hi - t0 : tt);
         const uint32_t c0 = ci * tc;
         const uint32_t nc_tile = (a.nchan - c0 < tc) ? a.nchan - c0 : tc;
-        const int64_t so = a.src ? a.src[f] : a.src0 + (int64_t)f * a.src_stride;
+        const int64_t so = bb_src_at(a, f);
         const bool valid = bb_src_ok(so, a.src_lim);
         const uint16_t *in = reinterpret_cast<const uint16_t *>(a.buf + (valid ? so : 0));
 

@@ -93,7 +93,7 @@ __device__ __forceinline__ void bb_xpose_body(const bb_tiled_args &a, uint32_t *
         const uint32_t ti = rem / a.nct, ci = rem - ti * a.nct;
         const uint32_t c0 = ci * TC;
         const uint32_t ncv = (a.nchan - c0 < TC) ? a.nchan - c0 : TC;
-        const int64_t so = a.src ? a.src[f] : a.src0 + (int64_t)f * a.src_stride;
+        const int64_t so = bb_src_at(a, f);
         valid = bb_src_ok(so, a.src_lim);
         const uint16_t *in = reinterpret_cast<const uint16_t *>(a.buf + (valid ? so : 0));
         // Addresses first (a mapped channel costs a look-up, and the wait for it also

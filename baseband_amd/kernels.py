@@ -558,7 +558,7 @@ def copy_frames(dbuf, nframes, nbytes_per_frame, src0=0, src_stride=0, out=None)
 STATES_MAX_ROW_BITS = 128      # chunk * bps the counting kernel takes (16 byte phases on chip)
 
 
-# -- what the calls on packed bytes share (count_states, count_states_bins, repack_frames)
+# -- what the calls on packed bytes share (count_states, count_states_bins, repack_frames, requant_frames)
 def _default_payload(bps, chunk):
     """The smallest payload of whole dwords and rows: what `*_supported` asks about by default."""
     return max(4, chunk * bps // 8) if bps in (1, 2, 4, 8) and chunk > 0 else 4
@@ -574,6 +574,16 @@ def _given(tensor, name, dtype):
     if tensor is not None and (tensor.dtype != dtype or not tensor.is_contiguous()):
         raise TypeError("{} must be a contiguous {} tensor".format(name, str(dtype).split('.')[-1]))
     return tensor is not None
+
+
+def _frames_out(call, precheck, name, dbuf, src, nframes, p, nrows, payload_out, row_bits, nslot, out):
+    """The end of `repack_frames` and `requant_frames`: without `out`, whole output frames (`nslot` payloads
+    with rows of `row_bits` bits) that hold the output rows [0, nrows); then the call."""
+    if not _given(out, 'out', torch.uint8):
+        check(precheck(C.byref(p)), name)                   # (before a shape is made of the parameters)
+        out = torch.empty(-(-nrows // (payload_out * 8 // row_bits)) * nslot * payload_out, dtype=torch.uint8, device=dbuf.device)
+    check(call(_ptr(dbuf), dbuf.numel(), _ptr(src), nframes, C.byref(p), _ptr(out), out.numel(), _stream(dbuf)), name)
+    return out
 
 
 def count_states_supported(bps, chunk=1, nslot=1, payload_nbytes=None):
@@ -666,13 +676,8 @@ def repack_frames(dbuf, nframes, payload_in, bps, coder_in, chunk_in, nslot_in, 
         row_hi = _all_rows(nframes, payload_in, bps, chunk_in)
     p = _lib.repack_params(bps, coder_in, coder_out, chunk_in, nslot_in, chunk_out, nslot_out, payload_in,
                            payload_out, fill_code, src0, src_stride, row_lo, row_hi, first_row)
-    if not _given(out, 'out', torch.uint8):
-        check(lib.bb_repack_check(C.byref(p)), 'bb_repack_frames')
-        nout = -(-(first_row + row_hi - row_lo) // (payload_out * 8 // bps // chunk_out))     # whole output frames
-        out = torch.empty(nout * nslot_out * payload_out, dtype=torch.uint8, device=dbuf.device)
-    check(lib.bb_repack_frames(_ptr(dbuf), dbuf.numel(), _ptr(src), nframes, C.byref(p),
-                               _ptr(out), out.numel(), _stream(dbuf)), 'bb_repack_frames')
-    return out
+    return _frames_out(lib.bb_repack_frames, lib.bb_repack_check, 'bb_repack_frames', dbuf, src, nframes, p,
+                       first_row + row_hi - row_lo, payload_out, bps * chunk_out, nslot_out, out)
 
 
 REQUANT_MAX_ROW_BITS = 256     # chunk * max(bps_in, bps_out) the requantize kernel takes
@@ -720,13 +725,8 @@ def requant_frames(dbuf, nframes, payload_in, bps_in, chunk, nslot, bps_out, pay
         row_hi = _all_rows(nframes, payload_in, bps_in, chunk)
     p = _lib.requant_params(bps_in, bps_out, chunk, nslot, payload_in, payload_out, table, fill_code,
                             src0, src_stride, row_lo, row_hi, first_row)
-    if not _given(out, 'out', torch.uint8):
-        check(lib.bb_requant_check(C.byref(p)), 'bb_requant_frames')
-        nout = -(-(first_row + row_hi - row_lo) // (payload_out * 8 // bps_out // chunk))     # whole output frames
-        out = torch.empty(nout * nslot * payload_out, dtype=torch.uint8, device=dbuf.device)
-    check(lib.bb_requant_frames(_ptr(dbuf), dbuf.numel(), _ptr(src), nframes, C.byref(p),
-                                _ptr(out), out.numel(), _stream(dbuf)), 'bb_requant_frames')
-    return out
+    return _frames_out(lib.bb_requant_frames, lib.bb_requant_check, 'bb_requant_frames', dbuf, src, nframes, p,
+                       first_row + row_hi - row_lo, payload_out, bps_out * chunk, nslot, out)
 
 
 TOUCH_MIN_BYTES = 16 << 20

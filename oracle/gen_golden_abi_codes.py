@@ -3,8 +3,9 @@
 replayed by tests/test_abi_codes.py.
 
 Run ONCE, at the commit whose answers are the expectation (the parent of a change to
-the host dispatch; last: the parent of the change that gave the packed-byte entries
-bb_count_states, bb_count_states_bins and bb_repack_frames their shared checks), on a
+the host dispatch; last: the parent of the change that moved the packed-byte entries
+bb_count_states, bb_count_states_bins, bb_repack_frames and bb_requant_frames into
+csrc/bb_packed.inc, which added the rows of bb_requant_frames), on a
 machine WITHOUT a device: every check runs before the first HIP call, so a call with
 one fault answers its code there and a call without a fault stops at BB_EIO.  Device
 addresses are made up; nothing follows them on the host.  The decode, encode, scan and
@@ -453,7 +454,7 @@ add('buffer not 8-byte aligned', d_buf=BUF + 4)
 add('nothing to read', nframes=0, n=0)
 add('nothing to read, selecting', nframes=0, n=0, nout=4)
 
-# ---- the packed-byte entries: statistics and repack -----------------------------------------
+# ---- the packed-byte entries: statistics, repack and requantize -----------------------------------------
 # Single faults as above, and DOUBLE faults: what a reordering of the checks would change
 # unseen.  A rule is (statement, label, changes): `statement` names the `if` of the entry
 # that answers it.  main() pairs the first rule of every statement with the first rule of
@@ -611,6 +612,66 @@ add('null parameter block', p=None)
 add('nframes 0, null buffers', nframes=0, p__row_hi=0, d_buf=None, buf_nbytes=0)
 add('second output frame one byte short', p__first_row=128, out_nbytes=67)
 
+
+def requant(**f):
+    d = dict(bps_in=2, bps_out=4, chunk=1, nslot=2, fill_code=0, reserved=0, payload_in=192, payload_out=64,
+             src0=0, src_stride=192, row_lo=0, row_hi=8, first_row=0, map=[0, 5, 10, 15])
+    d.update(f)
+    return S('RequantParams', **d)
+
+
+# 4 frame sets of 2 slots x 192 bytes (768 rows of one 2-bit code) -> payloads of 64 bytes, 128 rows of one 4-bit code
+add = rules('bb_requant_frames', RP,
+            dict(d_buf=BUF, buf_nbytes=8 * 192, d_src=None, nframes=4, p=requant(), d_out=OUT, out_nbytes=1 << 16, stream=None),
+            [
+                ('bps', '3 bits per sample in', dict(p__bps_in=3)),
+                ('bps', '3 bits per sample out', dict(p__bps_out=3)),
+                ('fields', 'reserved set', dict(p__reserved=1)),
+                ('fields', 'chunk 0', dict(p__chunk=0)),
+                ('fields', 'nslot 0', dict(p__nslot=0)),
+                ('pow2', 'chunk not a power of two', dict(p__chunk=3)),
+                ('pow2', 'nslot not a power of two', dict(p__nslot=3)),
+                ('slots', '64 slots', dict(p__nslot=64)),
+                ('row bits', 'rows of more than 256 bits', dict(p__chunk=128)),
+                ('payload in', 'payload_in not whole dwords', dict(p__payload_in=190)),
+                ('payload in', 'empty payload_in', dict(p__payload_in=0)),
+                ('payload in', 'payload_in above 2^56', dict(p__payload_in=(1 << 56) + 4)),
+                ('payload out', 'payload_out not whole dwords', dict(p__payload_out=62)),
+                ('payload out', 'empty payload_out', dict(p__payload_out=0)),
+                ('payload out', 'payload_out above 2^56', dict(p__payload_out=(1 << 56) + 4)),
+                ('whole rows in', 'payload_in not whole rows', dict(p__payload_in=196, p__chunk=32)),
+                ('whole rows out', 'payload_out not whole rows', dict(p__payload_out=68, p__chunk=16)),
+                ('fill', 'negative fill_code', dict(p__fill_code=-1)),
+                ('fill', 'fill_code 16', dict(p__fill_code=16)),
+                ('map', 'map entry 16 for 4 bits', dict(p__map=[0, 5, 10, 16])),
+                ('row order', 'row_lo past row_hi', dict(p__row_lo=16)),
+                ('output', 'null output', dict(d_out=None)),
+                ('output', 'output not 16-byte aligned', dict(d_out=OUT + 8)),
+                ('first_row', 'first_row above 2^56', dict(p__first_row=(1 << 56) + 8)),
+                ('whole bytes', 'first_row not a whole byte', dict(p__first_row=2)),
+                ('whole bytes', 'row_lo not a whole byte', dict(p__row_lo=2)),
+                ('whole bytes', 'row_hi not a whole byte', dict(p__row_hi=10)),
+                ('whole bytes', 'whole bytes in, not out', dict(p__bps_in=4, p__bps_out=2, p__payload_in=64, p__payload_out=192,
+                                                                 p__src_stride=64, p__map=[0, 1, 2, 3], p__row_hi=10)),
+                ('rows overflow', 'more rows than 64 bits count', dict(nframes=1 << 60)),
+                ('rows overflow', 'more bytes than 2^58', dict(d_src=SRC, nframes=1 << 20, p__payload_in=1 << 39)),
+                ('row range', 'row_hi past the last row', dict(p__row_hi=4 * 768 + 8)),
+                ('empty', 'no rows', dict(p__row_lo=8)),
+                ('empty', 'nframes 0', dict(nframes=0, p__row_hi=0)),
+                ('output frames', 'more output bytes than 2^58', dict(p__first_row=1 << 56, p__chunk=16)),
+                ('output range', 'output one byte short', dict(out_nbytes=67)),
+                ('buffer', 'null buffer', dict(d_buf=None)),
+                ('buffer', 'buffer not 4-byte aligned', dict(d_buf=BUF + 2)),
+                ('stride', 'misaligned src0', dict(p__src0=2)),
+                ('stride', 'negative src0', dict(p__src0=-4)),
+                ('stride', 'misaligned src_stride', dict(p__src_stride=194)),
+                ('stride', 'negative src_stride', dict(p__src_stride=-192)),
+                ('source range', 'source range one byte past the end', dict(buf_nbytes=8 * 192 - 1)),
+            ])
+add('null parameter block', p=None)
+add('nframes 0, null buffers', nframes=0, p__row_hi=0, d_buf=None, buf_nbytes=0)
+add('second output frame one byte short', p__first_row=128, out_nbytes=195)
+
 # pairs whose single-fault changes contradict each other, restated so that both faults stand
 PAIRED_BY_HAND = {
     'bb_count_states': [
@@ -626,6 +687,13 @@ PAIRED_BY_HAND = {
         ('whole bytes + first_row', dict(first_row=(1 << 56) + 2)),
     ],
     'bb_repack_frames': [
+        ('empty + row range', dict(p__row_lo=4 * 768 + 8, p__row_hi=4 * 768 + 8)),
+        ('empty + row range (nframes 0)', dict(nframes=0)),
+        ('empty + whole bytes', dict(p__row_lo=2, p__row_hi=2)),
+        ('whole bytes + row range', dict(p__row_hi=4 * 768 + 2)),
+        ('whole bytes + first_row', dict(p__first_row=(1 << 56) + 2)),
+    ],
+    'bb_requant_frames': [
         ('empty + row range', dict(p__row_lo=4 * 768 + 8, p__row_hi=4 * 768 + 8)),
         ('empty + row range (nframes 0)', dict(nframes=0)),
         ('empty + whole bytes', dict(p__row_lo=2, p__row_hi=2)),
@@ -672,6 +740,7 @@ def main():
     nsingle = len(CASES)
     print("{} pairs of statements, {} left out (contradicting changes)".format(*pair_cases({c['id']: c['code'] for c in CASES})))
     record(CASES[nsingle:])
+    CASES.sort(key=lambda c: c['fn'] == 'bb_requant_frames')         # recorded later: its rows stand behind the others'
     ids = [c['id'] for c in CASES]
     assert len(set(ids)) == len(ids), [i for i in ids if ids.count(i) > 1]
     path = os.path.join(ROOT, 'tests', 'golden', 'abi_return_codes.json')

@@ -2,8 +2,8 @@
 tests/golden/abi_return_codes.json was recorded (oracle/gen_golden_abi_codes.py, at
 the commit before the host dispatch was reorganised): one call per rule and entry
 point, a single fault each; for the packed-byte entries (bb_count_states,
-bb_count_states_bins, bb_repack_frames) also one call per pair of checks that answer
-different codes, which holds the order of their checks.
+bb_count_states_bins, bb_repack_frames, bb_requant_frames) also one call per pair of
+checks that answer different codes, which holds the order of their checks.
 
 The argument checks run before any HIP call, so no GPU is needed -- and none must be
 used: the calls carry made-up device addresses.  They are replayed in a child process
@@ -46,7 +46,7 @@ def test_table_covers_every_checked_entry_point():
                if n.startswith(('bb_decode_', 'bb_encode_')) or n.endswith(('_scan', '_scan_at', '_locate', '_read_window'))}
     checked -= {'bb_decode_out_check', 'bb_decode_frames_select_check'}           # (no buffers: tests/test_abi.py, test_half_abi.py)
     checked |= {'bb_copy_frames', 'bb_verify_records', 'bb_build_index', 'bb_mark4_header_crc', 'bb_mark5b_locate_stream',
-                'bb_count_states', 'bb_count_states_bins', 'bb_repack_frames'}
+                'bb_count_states', 'bb_count_states_bins', 'bb_repack_frames', 'bb_requant_frames'}
     assert fns == checked, fns ^ checked
     # an empty request, with a good and with a bad parameter block, for each output type
     for tn in ('f32', 'f16', 'bf16'):

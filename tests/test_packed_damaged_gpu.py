@@ -22,8 +22,9 @@ import numpy as np
 import pytest
 
 from conftest import golden_path, load_expected, load_file
+from packedkit import _torch, pack_codes
 from test_corrupt_gpu import CASES, _corrupt, FIXED, _fixed_blob
-from test_repack_kernels_gpu import MAPS, FILL_CODE, pack_codes, VDIF, MARK5B
+from test_repack_kernels_gpu import MAPS, FILL_CODE, VDIF, MARK5B
 from test_states_readers_gpu import open_on
 from test_convert_gpu import vdif_writer, m5b_writer
 
@@ -44,11 +45,6 @@ TARGETS = {
 }
 GEOMETRY = {'vdif': (VDIF, 20000, 8), 'm5b_fake': (MARK5B, 20000, 1), 'm5b_sample': (MARK5B, 5000, 1)}
 WAYS = [(how, before) for how in ('file', 'staged', 'device', 'short windows') for before in ('fresh', 'after a read')]
-
-
-def _torch():
-    import torch
-    return torch
 
 
 with open(golden_path('levels.json')) as _f:

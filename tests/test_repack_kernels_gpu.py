@@ -12,8 +12,7 @@ import numpy as np
 import pytest
 
 import guardkit
-from test_states_abi import unpack_codes
-from test_states_kernels_gpu import device, indexed_case, whole_rows
+from packedkit import _torch, unpack_codes, pack_codes, device, whole_rows, indexed_case, judge
 
 pytestmark = pytest.mark.gpu
 
@@ -30,19 +29,8 @@ CASES = [(i, o, bps) for i, o in SHAPES for bps in (1, 2, 4, 8) if i[0] * i[1] *
 PAYLOADS = ((40, 37), (104, 19), (8000, 5))                 # (bytes, frames); rounded up to whole rows
 
 
-def _torch():
-    import torch
-    return torch
-
-
 def pairs_of(bps):
     return [pair for pair, maps in sorted(MAPS.items()) if bps in maps]
-
-
-def pack_codes(codes, bps):
-    """Fields LSB first -> bytes: the inverse of unpack_codes."""
-    c = np.asarray(codes, np.uint8).reshape(-1, 8 // bps)
-    return (c << np.arange(0, 8, bps, dtype=np.uint8)).sum(1).astype(np.uint8)
 
 
 def byte_unit(bps, chunk_in, chunk_out):
@@ -105,15 +93,6 @@ def run(dbuf, nframes, payload_in, bps, pair, shape_in, shape_out, payload_out, 
                                 shape_out[1], shape_out[0], payload_out, fill_code=fill_code, out=out, **kw)
     assert got is out
     return whole, view, before
-
-
-def judge(whole, view, want, what):
-    """Exact bytes; nothing outside the view; words the request does not meet still poison."""
-    words = np.ascontiguousarray(want).view(np.uint32)
-    v = guardkit.verdict(whole, view, words)
-    untouched = int((words == guardkit.POISON).sum())
-    assert not v.touched and v.wrong == 0 and v.poison_left == untouched, \
-        (what, guardkit.describe(v, words.size), 'words that must stay poison: {}'.format(untouched))
 
 
 def payloads_out(payload_in, bps, shape_in, shape_out):

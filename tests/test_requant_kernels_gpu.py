@@ -13,10 +13,7 @@ import numpy as np
 import pytest
 
 import guardkit
-from test_states_abi import unpack_codes
-from test_states_kernels_gpu import device, indexed_case, whole_rows
-from test_repack_kernels_gpu import judge, pack_codes
-
+from packedkit import _torch, unpack_codes, pack_codes, device, whole_rows, indexed_case, judge
 
 pytestmark = pytest.mark.gpu
 
@@ -24,11 +21,6 @@ WIDTHS = (1, 2, 4, 8)
 PAIRS = [(bi, bo) for bi in WIDTHS for bo in WIDTHS]
 SHAPES = [(1, 1), (1, 8), (8, 1), (2, 2), (16, 1), (32, 1)]     # (nslot, chunk); every row fits 256 bits
 PAYLOADS = ((40, 37), (104, 19), (8000, 5))                     # (bytes, frames); rounded up to whole rows
-
-
-def _torch():
-    import torch
-    return torch
 
 
 def byte_unit(bps_in, bps_out, chunk):

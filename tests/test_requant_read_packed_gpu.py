@@ -8,8 +8,8 @@ import numpy as np
 import pytest
 
 from conftest import golden_path
+from packedkit import unpack_codes
 from test_convert_gpu import T_M5B, invalid_sample_vdif, open_m5b, open_vdif
-from test_states_abi import unpack_codes
 
 pytestmark = pytest.mark.gpu
 

@@ -10,19 +10,15 @@ import ctypes
 import numpy as np
 import pytest
 
-from test_states_abi import SUPPORTED, unpack_codes
-from test_states_kernels_gpu import device, expected, indexed_case, whole_rows
+from packedkit import _torch, unpack_codes, device, whole_rows, indexed_case
+from test_states_abi import SUPPORTED
+from test_states_kernels_gpu import expected
 
 pytestmark = pytest.mark.gpu
 
 GEOMETRIES = [(bps, chunk) for bps, chunk in SUPPORTED if chunk << bps <= 1024]
 PAYLOADS = ((40, 37), (104, 19), (8000, 5))                 # (bytes, frames); rounded up to whole rows
 MAX_COUNTERS = 1 << 22                                      # of one expectation
-
-
-def _torch():
-    import torch
-    return torch
 
 
 class Codes:

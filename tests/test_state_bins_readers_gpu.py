@@ -9,15 +9,10 @@ import numpy as np
 import pytest
 
 from conftest import golden_path
-from test_states_abi import unpack_codes
+from packedkit import _torch, unpack_codes
 from test_states_readers_gpu import FILES, numpy_counts, open_on, shaped, threads_complex, written_vdif
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch():
-    import torch
-    return torch
 
 
 def file_codes(fh, image):

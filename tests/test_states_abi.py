@@ -6,13 +6,7 @@ import ctypes
 import numpy as np
 import pytest
 
-
-def unpack_codes(raw, bps):
-    """The raw codes of payload bytes, fields LSB first: code e is field e % (8/bps) of
-    byte e / (8/bps) (vdif/payload.py:25-103, mark5b/payload.py:27-94)."""
-    raw = np.asarray(raw, np.uint8).ravel()
-    shifts = np.arange(0, 8, bps, dtype=np.uint8)
-    return ((raw[:, None] >> shifts) & ((1 << bps) - 1)).ravel()
+from packedkit import unpack_codes
 
 
 def test_struct_layout():

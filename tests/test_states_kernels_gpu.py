@@ -7,14 +7,9 @@ import ctypes
 import numpy as np
 import pytest
 
-from test_states_abi import unpack_codes
+from packedkit import _torch, unpack_codes, device, whole_rows, indexed_case
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch():
-    import torch
-    return torch
 
 
 def expected(buf, src, nframes, payload, bps, chunk, nslot, row_lo=0, row_hi=None):
@@ -38,38 +33,12 @@ def expected(buf, src, nframes, payload, bps, chunk, nslot, row_lo=0, row_hi=Non
     return out
 
 
-def device(a):
-    return _torch().from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 def largest_chunk(bps):
     return 128 // bps
 
 
 GEOMETRIES = [(bps, chunk) for bps in (1, 2, 4, 8) for chunk in (1, 2, 8, largest_chunk(bps))]
 PAYLOADS = ((8, 37), (260, 19), (1000, 11), (8000, 5), (70000, 2))      # (bytes, frames)
-
-
-def whole_rows(nbytes, bps, chunk):
-    unit = max(4, chunk * bps // 8)
-    return -(-nbytes // unit) * unit
-
-
-def indexed_case(rng, payload, nframes, nslot):
-    """A buffer of payloads 20 bytes apart, three of them at odd byte addresses, and an
-    index over them: shuffled, with missing entries and entries that leave the buffer."""
-    n = nframes * nslot
-    step = payload + 20
-    buf = rng.integers(0, 256, 16 + n * step, dtype=np.uint8)
-    src = 16 + np.arange(n, dtype=np.int64) * step
-    src[1 % n] += 1
-    src[2 % n] += 2
-    src[3 % n] += 3
-    rng.shuffle(src)
-    bad = [-1, -1, len(buf) - payload + 4, -(1 << 33), len(buf) + (1 << 40)]
-    for k, b in zip(rng.choice(n, size=min(n - 1, len(bad)), replace=False), bad):
-        src[k] = b
-    return buf, src
 
 
 @pytest.mark.parametrize('bps,chunk', GEOMETRIES)

@@ -8,14 +8,9 @@ import numpy as np
 import pytest
 
 from conftest import golden_path, load_file
-from test_states_abi import unpack_codes
+from packedkit import _torch, unpack_codes
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch():
-    import torch
-    return torch
 
 
 # -- the files -------------------------------------------------------------------------
