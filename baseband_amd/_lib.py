@@ -145,6 +145,16 @@ class RequantParams(C.Structure):
                 ('map', C.c_uint8 * 256)]
 
 
+class RecodeParams(C.Structure):
+    _fields_ = [('bps_in', C.c_int32), ('bps_out', C.c_int32), ('chunk_in', C.c_int32),
+                ('nslot_in', C.c_int32), ('chunk_out', C.c_int32), ('nslot_out', C.c_int32),
+                ('fill_code', C.c_int32), ('reserved', C.c_int32),
+                ('payload_in', C.c_uint64), ('payload_out', C.c_uint64),
+                ('src0', C.c_int64), ('src_stride', C.c_int64),
+                ('row_lo', C.c_uint64), ('row_hi', C.c_uint64), ('first_row', C.c_uint64),
+                ('map', C.c_uint8 * 256)]
+
+
 class Mark4ScanParams(C.Structure):
     _fields_ = [('first_offset', C.c_uint64), ('ntrack', C.c_int32),
                 ('ref_year', C.c_int32), ('ref_qms', C.c_int64),
@@ -237,6 +247,8 @@ SIGNATURES = [
     ('bb_repack_check', C.c_int, [C.POINTER(RepackParams)]),
     ('bb_requant_frames', C.c_int, [_vp, _sz, _vp, _sz, C.POINTER(RequantParams), _vp, _sz, _vp]),
     ('bb_requant_check', C.c_int, [C.POINTER(RequantParams)]),
+    ('bb_recode_frames', C.c_int, [_vp, _sz, _vp, _sz, C.POINTER(RecodeParams), _vp, _sz, _vp]),
+    ('bb_recode_check', C.c_int, [C.POINTER(RecodeParams)]),
     ('bb_fetch_counter', C.c_int, [_vp, _vp, _vp, _vp]),
     ('bb_mark5b_read_window', C.c_int, [_vp, _sz, C.POINTER(Mark5BScanParams), _sz, _sz, C.POINTER(DecodeParams),
                                         _vp, C.c_int, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
@@ -347,6 +359,18 @@ def repack_check(bps, coder_in, coder_out, chunk_in, nslot_in, chunk_out, nslot_
     return lib.bb_repack_check(C.byref(p))
 
 
+def _set_table(p, table, name):
+    """`table` -> the `map` of a parameter block: at most 256 codes of 0 .. 255 (the rest are 0)."""
+    import numpy as np
+    codes = np.asarray(table if isinstance(table, np.ndarray) else list(table), dtype=np.int64).reshape(-1)
+    if codes.size > 256 or ((codes < 0) | (codes > 255)).any():
+        raise ValueError("{}: a table is at most 256 codes of 0 .. 255".format(name))
+    full = np.zeros(256, np.uint8)
+    full[:codes.size] = codes
+    C.memmove(p.map, full.ctypes.data, 256)
+    return p
+
+
 def requant_params(bps_in, bps_out, chunk, nslot, payload_in, payload_out, table=(), fill_code=0, src0=0,
                    src_stride=0, row_lo=0, row_hi=0, first_row=0, reserved=0):
     """`table`: output code by input code, at most 256 entries of 0 .. 255 (the rest are 0)."""
@@ -354,14 +378,7 @@ def requant_params(bps_in, bps_out, chunk, nslot, payload_in, payload_out, table
     p.bps_in, p.bps_out, p.chunk, p.nslot, p.fill_code, p.reserved = bps_in, bps_out, chunk, nslot, fill_code, reserved
     p.payload_in, p.payload_out, p.src0, p.src_stride = payload_in, payload_out, src0, src_stride
     p.row_lo, p.row_hi, p.first_row = row_lo, row_hi, first_row
-    import numpy as np
-    codes = np.asarray(table if isinstance(table, np.ndarray) else list(table), dtype=np.int64).reshape(-1)
-    if codes.size > 256 or ((codes < 0) | (codes > 255)).any():
-        raise ValueError("requant_params: a table is at most 256 codes of 0 .. 255")
-    full = np.zeros(256, np.uint8)
-    full[:codes.size] = codes
-    C.memmove(p.map, full.ctypes.data, 256)
-    return p
+    return _set_table(p, table, 'requant_params')
 
 
 def requant_check(bps_in, bps_out, chunk, nslot, payload_in, payload_out, table=(), fill_code=0,
@@ -371,6 +388,26 @@ def requant_check(bps_in, bps_out, chunk, nslot, payload_in, payload_out, table=
     p = requant_params(bps_in, bps_out, chunk, nslot, payload_in, payload_out, table, fill_code, 0, 0,
                        row_lo, row_hi, first_row, reserved)
     return lib.bb_requant_check(C.byref(p))
+
+
+def recode_params(bps_in, bps_out, chunk_in, nslot_in, chunk_out, nslot_out, payload_in, payload_out, table=(),
+                  fill_code=0, src0=0, src_stride=0, row_lo=0, row_hi=0, first_row=0, reserved=0):
+    """`table`: output code by input code, at most 256 entries of 0 .. 255 (the rest are 0)."""
+    p = RecodeParams()
+    p.bps_in, p.bps_out, p.fill_code, p.reserved = bps_in, bps_out, fill_code, reserved
+    p.chunk_in, p.nslot_in, p.chunk_out, p.nslot_out = chunk_in, nslot_in, chunk_out, nslot_out
+    p.payload_in, p.payload_out, p.src0, p.src_stride = payload_in, payload_out, src0, src_stride
+    p.row_lo, p.row_hi, p.first_row = row_lo, row_hi, first_row
+    return _set_table(p, table, 'recode_params')
+
+
+def recode_check(bps_in, bps_out, chunk_in, nslot_in, chunk_out, nslot_out, payload_in, payload_out, table=(),
+                 fill_code=0, row_lo=0, row_hi=0, first_row=0, reserved=0):
+    """What `bb_recode_frames` would answer to these parameters, as far as they decide it
+    (bb_recode_check: no buffers, no device): BB_OK, BB_EINVAL or BB_ENOTSUP."""
+    p = recode_params(bps_in, bps_out, chunk_in, nslot_in, chunk_out, nslot_out, payload_in, payload_out, table,
+                      fill_code, 0, 0, row_lo, row_hi, first_row, reserved)
+    return lib.bb_recode_check(C.byref(p))
 
 
 def out_type_of(dtype):

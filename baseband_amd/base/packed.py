@@ -354,7 +354,8 @@ class PackedBytesMixin:
 
         return self._answer_packed(answer, strict=True)
 
-    def read_packed(self, count, coder, nthread, nchan, samples_per_frame, fill_code, bps=None, scale=None):
+    def read_packed(self, count, coder, nthread, nchan, samples_per_frame, fill_code, bps=None, scale=None,
+                    regroup=False):
         """The next `count` samples as packed payloads of another frame geometry, without
         decoding them (bb_repack_frames) -> ``(payloads, valid)``: a uint8 device tensor of
         shape ``(count // samples_per_frame, nthread, payload_nbytes)`` holding what a
@@ -373,6 +374,14 @@ class PackedBytesMixin:
         both sides (`nthread` threads of as many codes per sample as the reader's), else
         NotImplementedError; `fill_code` is a code of `bps` bits and is not mapped.
 
+        With ``regroup=True`` such a request may change the thread structure as well
+        (`nthread` threads of `nchan` channels against the reader's, as from 8-bit VDIF with
+        one channel per thread to 2-bit VDIF with one thread, or to Mark 5B): permutation
+        and table are then one pass (bb_recode_frames).  Both sides must have the same
+        number of components (threads times codes per sample), else NotImplementedError.
+        Requests that keep the thread structure, or that do not requantize, go the same
+        way with and without it.
+
         A read in every respect but the decoding: a damaged file is repaired under
         ``verify='fix'`` as ``read(count)`` repairs it (the frames are located and the
         whole request is answered through that index), and ``verify=True`` raises what
@@ -389,11 +398,22 @@ class PackedBytesMixin:
         if samples_per_frame * chunk_out * bps_out % 32:
             raise ValueError("read_packed: payloads are whole 32-bit words")
         payload_out = samples_per_frame * chunk_out * bps_out // 8
-        if requant:
-            if nthread != g.nslot or chunk_out != g.chunk:
+        recode = requant and (nthread != g.nslot or chunk_out != g.chunk)
+        if recode:
+            if not regroup:
                 raise NotImplementedError(
                     "read_packed: a change of sample width or scale keeps the thread structure ({} x {} codes "
+                    "-> {} x {}) unless regroup=True".format(g.nslot, g.chunk, nthread, chunk_out))
+            if nthread * chunk_out != g.nslot * g.chunk:
+                raise NotImplementedError(
+                    "read_packed: a change of sample width or scale keeps the number of components ({} x {} codes "
                     "-> {} x {})".format(g.nslot, g.chunk, nthread, chunk_out))
+            if not kernels.recode_supported(g.bps, bps_out, g.chunk, g.nslot, chunk_out, nthread,
+                                            g.payload_nbytes, payload_out):
+                raise NotImplementedError(
+                    "read_packed: {} x {} codes of {} bits -> {} x {} codes of {} bits is not a conversion the "
+                    "recode kernel takes".format(g.nslot, g.chunk, g.bps, nthread, chunk_out, bps_out))
+        elif requant:
             if not kernels.requant_supported(g.bps, bps_out, g.chunk, g.nslot, g.payload_nbytes, payload_out):
                 raise NotImplementedError(
                     "read_packed: {} x {} codes of {} bits -> {} bits is not a conversion the requantize "
@@ -419,7 +439,11 @@ class PackedBytesMixin:
             marks = _ValidityMarks(nout, samples_per_frame, start, stop, self.samples_per_frame, g.nslot)
 
             def visit(dbuf, src, s, e, row_lo, row_hi, first_row):
-                if requant:
+                if recode:
+                    kernels.recode_frames(dbuf, e - s, g.payload_nbytes, g.bps, g.chunk, g.nslot, bps_out, chunk_out,
+                                          nthread, payload_out, table, fill_code=fill_code, src=src, row_lo=row_lo,
+                                          row_hi=row_hi, first_row=first_row, out=out.reshape(-1))
+                elif requant:
                     kernels.requant_frames(dbuf, e - s, g.payload_nbytes, g.bps, g.chunk, g.nslot, bps_out, payload_out,
                                            table, fill_code=fill_code, src=src, row_lo=row_lo, row_hi=row_hi,
                                            first_row=first_row, out=out.reshape(-1))

@@ -1,5 +1,5 @@
 // The packed-byte entries of bbdecode.hip (bb_count_states, bb_count_states_bins, bb_repack_frames,
-// bb_requant_frames), their argument checks and what they share.  The ORDER of the checks is part of
+// bb_requant_frames, bb_recode_frames), their argument checks and what they share.  The ORDER of the checks is part of
 // the ABI: tests/golden/abi_return_codes.json holds it in place.
 extern "C++" { namespace {                                   // (the entries have C linkage: the include stands among them)
 // A slot's stream of rows: payloads of whole dwords that hold whole rows of `chunk` codes
@@ -330,3 +330,67 @@ int bb_requant_frames(const void *d_buf, size_t buf_nbytes, const int64_t *d_src
     return BB_OK;
 }
 
+
+// ---- conversion between sample widths across thread layouts on the packed bytes (k_recode.h):
+//      bb_repack_frames' permutation of components with bb_requant_frames' table ----
+static int recode_params_check(const bb_recode_params *p, uint64_t *R_in, uint64_t *R_out)
+{
+    if (!p) return BB_EINVAL;
+    if (log2_bps(p->bps_in) < 0 || log2_bps(p->bps_out) < 0) return BB_ENOTSUP;
+    if (p->reserved != 0 || p->chunk_in < 1 || p->nslot_in < 1 || p->chunk_out < 1 || p->nslot_out < 1) return BB_EINVAL;
+    if ((p->chunk_in & (p->chunk_in - 1)) || (p->nslot_in & (p->nslot_in - 1)) ||
+        (p->chunk_out & (p->chunk_out - 1)) || (p->nslot_out & (p->nslot_out - 1))) return BB_ENOTSUP;
+    if ((int64_t)p->nslot_in * p->chunk_in != (int64_t)p->nslot_out * p->chunk_out) return BB_EINVAL;
+    if ((uint32_t)p->nslot_in > BB_RECODE_MAX_SLOTS || (uint32_t)p->nslot_out > BB_RECODE_MAX_SLOTS) return BB_ENOTSUP;
+    if ((int64_t)p->nslot_in * p->chunk_in * std::max(p->bps_in, p->bps_out) > (int64_t)BB_RECODE_MAX_ROW_BITS) return BB_ENOTSUP;
+    if (slot_rows(p->payload_in, p->bps_in, p->chunk_in, R_in) ||
+        slot_rows(p->payload_out, p->bps_out, p->chunk_out, R_out)) return BB_EINVAL;
+    if (p->fill_code < 0 || p->fill_code >= (1 << p->bps_out)) return BB_EINVAL;
+    for (int c = 0; c < (1 << p->bps_in); ++c)
+        if ((int)p->map[c] >= (1 << p->bps_out)) return BB_EINVAL;
+    if (p->row_lo > p->row_hi) return BB_EINVAL;
+    return BB_OK;
+}
+
+int bb_recode_check(const bb_recode_params *p) { uint64_t R_in, R_out; return recode_params_check(p, &R_in, &R_out); }
+
+int bb_recode_frames(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size_t nframes,
+                     const bb_recode_params *p, void *d_out, size_t out_nbytes, void *stream)
+{
+    uint64_t R_in, R_out; packed_out o;
+    int rc = recode_params_check(p, &R_in, &R_out);
+    if (rc) return rc;
+    const uint64_t bi = (uint64_t)p->chunk_in * (uint64_t)p->bps_in, bo = (uint64_t)p->chunk_out * (uint64_t)p->bps_out;   // bits per row and slot
+    rc = packed_output(d_out, out_nbytes, nframes, p->payload_in, R_in, R_out, p->payload_out, (uint64_t)p->nslot_out, bi, bo,
+                       p->row_lo, p->row_hi, p->first_row, &o);
+    if (rc || !o.nrows) return rc;
+    bb_recode_args a;
+    rc = packed_source(a, d_buf, buf_nbytes, d_src, p->src0, p->src_stride,
+                       (uint64_t)nframes * (uint64_t)p->nslot_in, p->payload_in);
+    if (rc) return rc;
+    a.out = (uint8_t *)d_out;
+    a.buf_n = buf_nbytes;
+    a.pay_in = p->payload_in; a.pay_out = p->payload_out;
+    a.row_lo = p->row_lo; a.first_row = p->first_row; a.nrows = o.nrows;
+    a.R_out = R_out;
+    a.F0 = p->first_row / R_out;
+    a.nslot_in = (uint32_t)p->nslot_in; a.nslot_out = (uint32_t)p->nslot_out;
+    a.lbi = ceil_log2(bi); a.lbo = ceil_log2(bo);
+    a.lpi = (uint32_t)log2_bps(p->bps_in); a.lpo = (uint32_t)log2_bps(p->bps_out);
+    // the wider side of an item is 8 KiB; at least 256 rows: 32 bytes or more of every slot on either side
+    a.T = BB_RECODE_ITEM_BITS / ((uint32_t)p->nslot_in * (uint32_t)p->chunk_in * (uint32_t)std::max(p->bps_in, p->bps_out));
+    a.sstride = ((a.T << a.lbi) >> 3) + BB_REPACK_SLACK;
+    a.nseg = (R_out + a.T - 1) / a.T;
+    const uint64_t nf = o.f_last - a.F0 + 1;
+    if (nf > (~0ull) / a.nseg) return BB_ERANGE;
+    a.nwork = nf * a.nseg;
+    // the codes that stay adjacent on both sides, as far as a dword of either side holds them
+    a.lgc = std::min(std::min(ceil_log2((uint32_t)p->chunk_in), ceil_log2((uint32_t)p->chunk_out)), std::min(5u - a.lpi, 5u - a.lpo));
+    a.fill = (uint32_t)p->fill_code;
+    uint8_t *m = reinterpret_cast<uint8_t *>(a.map);                          // (entries the input cannot have: 0)
+    for (int c = 0; c < 256; ++c) m[c] = c < (1 << p->bps_in) ? p->map[c] : 0;
+    const dim3 grid = wave_grid(a.nwork);
+    hipLaunchKernelGGL(k_recode, grid, dim3(BB_BLOCK), 0, (hipStream_t)stream, a);
+    BB_HIP(hipGetLastError());
+    return BB_OK;
+}

@@ -16,6 +16,7 @@
 #include "k_state_bins.h"
 #include "k_repack.h"
 #include "k_requant.h"
+#include "k_recode.h"
 #include "k_tfpick.h"
 #if BB_EXP
 #include "k_burst.h"

@@ -558,7 +558,8 @@ def copy_frames(dbuf, nframes, nbytes_per_frame, src0=0, src_stride=0, out=None)
 STATES_MAX_ROW_BITS = 128      # chunk * bps the counting kernel takes (16 byte phases on chip)
 
 
-# -- what the calls on packed bytes share (count_states, count_states_bins, repack_frames, requant_frames)
+# -- what the calls on packed bytes share (count_states, count_states_bins, repack_frames, requant_frames,
+#    recode_frames)
 def _default_payload(bps, chunk):
     """The smallest payload of whole dwords and rows: what `*_supported` asks about by default."""
     return max(4, chunk * bps // 8) if bps in (1, 2, 4, 8) and chunk > 0 else 4
@@ -577,7 +578,7 @@ def _given(tensor, name, dtype):
 
 
 def _frames_out(call, precheck, name, dbuf, src, nframes, p, nrows, payload_out, row_bits, nslot, out):
-    """The end of `repack_frames` and `requant_frames`: without `out`, whole output frames (`nslot` payloads
+    """The end of `repack_frames`, `requant_frames` and `recode_frames`: without `out`, whole output frames (`nslot` payloads
     with rows of `row_bits` bits) that hold the output rows [0, nrows); then the call."""
     if not _given(out, 'out', torch.uint8):
         check(precheck(C.byref(p)), name)                   # (before a shape is made of the parameters)
@@ -727,6 +728,42 @@ def requant_frames(dbuf, nframes, payload_in, bps_in, chunk, nslot, bps_out, pay
                             src0, src_stride, row_lo, row_hi, first_row)
     return _frames_out(lib.bb_requant_frames, lib.bb_requant_check, 'bb_requant_frames', dbuf, src, nframes, p,
                        first_row + row_hi - row_lo, payload_out, bps_out * chunk, nslot, out)
+
+
+RECODE_MAX_ROW_BITS = 256      # nslot * chunk * max(bps_in, bps_out) the recode kernel takes
+RECODE_MAX_SLOTS = 32          # ... and thread slots on either side
+
+
+def recode_supported(bps_in, bps_out, chunk_in, nslot_in, chunk_out, nslot_out, payload_in=None, payload_out=None):
+    """Would `recode_frames` take these widths and this change of thread structure?  (bb_recode_check; no
+    device needed.)"""
+    if payload_in is None:
+        payload_in = _default_payload(bps_in, chunk_in)
+    if payload_out is None:
+        payload_out = _default_payload(bps_out, chunk_out)
+    return _lib.recode_check(bps_in, bps_out, chunk_in, nslot_in, chunk_out, nslot_out,
+                             payload_in, payload_out) == _lib.BB_OK
+
+
+def recode_frames(dbuf, nframes, payload_in, bps_in, chunk_in, nslot_in, bps_out, chunk_out, nslot_out, payload_out,
+                  table, fill_code=0, src=None, src0=0, src_stride=0, row_lo=0, row_hi=None, first_row=0, out=None):
+    """Conversion between sample widths across thread structures on the packed bytes
+    (bb_recode_frames): `repack_frames` with the table of `requant_frames` in place of the
+    coder pair.  Rows [row_lo, row_hi) of `nframes` input frame(set)s of `nslot_in` payloads
+    with `chunk_in` codes of `bps_in` bits per row, taken through the index `src` (-1 or an
+    offset outside the buffer: `fill_code`, not mapped) or at ``src0 + k * src_stride``,
+    become output rows ``first_row + (r - row_lo)`` of payloads of `nslot_out` slots with
+    `chunk_out` codes of `bps_out` bits per row, code c as ``table[c]`` -> uint8 device tensor
+    of whole output frames, payload (F, t) at ``(F * nslot_out + t) * payload_out``.  With
+    `out` (such a tensor, contiguous) only the bytes of the rows written change.  The row
+    range and `first_row` are whole bytes of every slot stream on both sides.  Nothing is
+    decoded and nothing synchronises."""
+    if row_hi is None:
+        row_hi = _all_rows(nframes, payload_in, bps_in, chunk_in)
+    p = _lib.recode_params(bps_in, bps_out, chunk_in, nslot_in, chunk_out, nslot_out, payload_in, payload_out, table,
+                           fill_code, src0, src_stride, row_lo, row_hi, first_row)
+    return _frames_out(lib.bb_recode_frames, lib.bb_recode_check, 'bb_recode_frames', dbuf, src, nframes, p,
+                       first_row + row_hi - row_lo, payload_out, bps_out * chunk_out, nslot_out, out)
 
 
 TOUCH_MIN_BYTES = 16 << 20

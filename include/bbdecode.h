@@ -847,6 +847,69 @@ int bb_requant_frames(const void *d_buf, size_t buf_nbytes,
                       void *d_out, size_t out_nbytes, void *stream);
 int bb_requant_check(const bb_requant_params *params);
 
+/*
+ * Conversion between sample widths ACROSS thread layouts on the packed bytes:
+ * bb_repack_frames' permutation of components with bb_requant_frames' table in
+ * place of the coder pair, in one pass (8-bit VDIF of one channel per thread ->
+ * 2-bit VDIF of one thread, or 2-bit Mark 5B).  Input exactly as for those two:
+ * frame-slot (f, s) has its payload_in bytes at d_src[f * nslot_in + s] (-1,
+ * any negative offset or a payload not wholly inside the buffer: a source that
+ * counts nothing) or, with d_src == NULL, at src0 + (f * nslot_in + s) *
+ * src_stride (multiples of 4; the last payload inside the buffer, else
+ * BB_ERANGE).  A row has nslot_in * chunk_in = nslot_out * chunk_out
+ * components; fields are LSB first.  With R_in = payload_in * 8 / bps_in /
+ * chunk_in and R_out = payload_out * 8 / bps_out / chunk_out rows per frame,
+ * component k = s * chunk_in + p of input row r has the code c in field
+ * (r % R_in) * chunk_in + p (of bps_in bits) of payload (r / R_in, s).  Counted
+ * row r in [row_lo, row_hi) has the output row G = first_row + (r - row_lo),
+ * and with t = k / chunk_out, q = k % chunk_out
+ *     field (G % R_out) * chunk_out + q (of bps_out bits) of output payload
+ *     (G / R_out, t) = map[c]
+ * or fill_code (not mapped) where the source counts nothing; payload (F, t)
+ * lies at (F * nslot_out + t) * payload_out.  Nothing outside the buffer is
+ * read; output bytes outside the rows written are not touched, so one request
+ * may be split over several calls into one output buffer.
+ *
+ * row_lo, row_hi and first_row must fall on a byte boundary of every input and
+ * every output slot stream (times chunk_in * bps_in and times chunk_out *
+ * bps_out a multiple of 8), else BB_ENOTSUP: whole bytes only.  BB_ERANGE:
+ * row_hi > nframes * R_in, the last output row beyond out_nbytes, the last
+ * fixed-stride payload outside the buffer.  BB_EINVAL: NULL pointers, d_buf not
+ * 4-byte or d_out not 16-byte aligned, and what bb_recode_check answers with
+ * it.  Stream-ordered, never allocates, never synchronises; nframes == 0 or
+ * row_lo == row_hi launches nothing; an argument error leaves d_out untouched.
+ *
+ * bb_recode_check answers what the parameters alone decide (no buffers, no
+ * device), in this order: a NULL block (BB_EINVAL); a width not in {1, 2, 4, 8}
+ * (BB_ENOTSUP); reserved != 0 or a chunk or slot count below 1 (BB_EINVAL); a
+ * chunk or slot count that is not a power of two (BB_ENOTSUP); nslot_in *
+ * chunk_in != nslot_out * chunk_out (BB_EINVAL); more than 32 slots on a side
+ * (BB_ENOTSUP); nslot * chunk * max(bps_in, bps_out) > 256 (BB_ENOTSUP);
+ * payloads that are 0, not multiples of 4 or not whole rows (BB_EINVAL);
+ * fill_code, then a used table entry, outside [0, 1 << bps_out) (BB_EINVAL);
+ * row_lo > row_hi (BB_EINVAL).
+ */
+typedef struct bb_recode_params {
+    int32_t  bps_in, bps_out;   /* 1, 2, 4, 8 each */
+    int32_t  chunk_in;          /* codes per (sample, slot) of the input; a power of two */
+    int32_t  nslot_in;          /* thread slots of the input; a power of two */
+    int32_t  chunk_out, nslot_out;
+    int32_t  fill_code;         /* output code written where a source counts nothing */
+    int32_t  reserved;          /* 0 */
+    uint64_t payload_in;        /* bytes per frame and slot; multiples of 4; whole rows */
+    uint64_t payload_out;
+    int64_t  src0, src_stride;  /* used when d_src == NULL, as in bb_decode_frames */
+    uint64_t row_lo, row_hi;    /* rows [row_lo, row_hi) of the request's nframes * R_in */
+    uint64_t first_row;         /* output row of row_lo */
+    uint8_t  map[256];          /* output code by input code; entries >= 1 << bps_in are ignored */
+} bb_recode_params;
+
+int bb_recode_frames(const void *d_buf, size_t buf_nbytes,
+                     const int64_t *d_src, size_t nframes,
+                     const bb_recode_params *params,
+                     void *d_out, size_t out_nbytes, void *stream);
+int bb_recode_check(const bb_recode_params *params);
+
 /* ---- byte-aligned formats with an axis permutation --------------------- */
 
 /*
