@@ -249,6 +249,8 @@ SIGNATURES = [
     ('bb_requant_check', C.c_int, [C.POINTER(RequantParams)]),
     ('bb_recode_frames', C.c_int, [_vp, _sz, _vp, _sz, C.POINTER(RecodeParams), _vp, _sz, _vp]),
     ('bb_recode_check', C.c_int, [C.POINTER(RecodeParams)]),
+    ('bb_recode_frames_tables', C.c_int, [_vp, _sz, _vp, _sz, C.POINTER(RecodeParams), _vp, _sz, _vp, _sz, _vp]),
+    ('bb_recode_tables_check', C.c_int, [C.POINTER(RecodeParams)]),
     ('bb_fetch_counter', C.c_int, [_vp, _vp, _vp, _vp]),
     ('bb_mark5b_read_window', C.c_int, [_vp, _sz, C.POINTER(Mark5BScanParams), _sz, _sz, C.POINTER(DecodeParams),
                                         _vp, C.c_int, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
@@ -408,6 +410,15 @@ def recode_check(bps_in, bps_out, chunk_in, nslot_in, chunk_out, nslot_out, payl
     p = recode_params(bps_in, bps_out, chunk_in, nslot_in, chunk_out, nslot_out, payload_in, payload_out, table,
                       fill_code, 0, 0, row_lo, row_hi, first_row, reserved)
     return lib.bb_recode_check(C.byref(p))
+
+
+def recode_tables_check(bps_in, bps_out, chunk_in, nslot_in, chunk_out, nslot_out, payload_in, payload_out,
+                        fill_code=0, row_lo=0, row_hi=0, first_row=0, reserved=0):
+    """What `bb_recode_frames_tables` would answer to these parameters, as far as they decide it
+    (bb_recode_tables_check: no buffers, no device; the block's own map stays zero)."""
+    p = recode_params(bps_in, bps_out, chunk_in, nslot_in, chunk_out, nslot_out, payload_in, payload_out, (),
+                      fill_code, 0, 0, row_lo, row_hi, first_row, reserved)
+    return lib.bb_recode_tables_check(C.byref(p))
 
 
 def out_type_of(dtype):

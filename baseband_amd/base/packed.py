@@ -354,6 +354,21 @@ class PackedBytesMixin:
 
         return self._answer_packed(answer, strict=True)
 
+    def _component_gains(self, scale, g):
+        """An array `scale` of `read_packed` -> float32 gains, one per component of a row: broadcast to the
+        reader's ``(nthread, nchan)`` (Mark 5B: ``(nchan,)``), a complex channel's gain on (re, im) alike."""
+        shape = tuple(self._packed_shape(torch.empty((g.nslot, g.chunk, 1), device='meta')).shape[:-1])
+        shape = shape[:-1] if self.complex_data else shape
+        gains = np.asarray(scale.detach().cpu() if torch.is_tensor(scale) else scale, dtype=np.float32)
+        try:
+            gains = np.broadcast_to(gains, shape)
+        except ValueError:
+            raise ValueError("read_packed: a scale of shape {} does not broadcast to the reader's {}"
+                             .format(tuple(gains.shape), shape)) from None
+        if not np.isfinite(gains).all():
+            raise ValueError("read_packed: scale must be finite")
+        return np.repeat(gains.reshape(-1), 2 if self.complex_data else 1)
+
     def read_packed(self, count, coder, nthread, nchan, samples_per_frame, fill_code, bps=None, scale=None,
                     regroup=False):
         """The next `count` samples as packed payloads of another frame geometry, without
@@ -382,6 +397,17 @@ class PackedBytesMixin:
         Requests that keep the thread structure, or that do not requantize, go the same
         way with and without it.
 
+        `scale` may also be an array or tensor that broadcasts to the reader's ``(nthread,
+        nchan)`` after thread selection (Mark 5B: ``(nchan,)``): one float32 gain per channel,
+        a complex channel's on its real and imaginary component alike, as in
+        ``fw.write(fr.read(n) * scale)``.  Every component of a row then has a table of its
+        own (``kernels.requant_tables``, bb_recode_frames_tables), whether or not the thread
+        structure changes; a change still needs ``regroup=True``.  A shape that does not
+        broadcast and gains that are not finite are ValueError.  `fill_code` stays ONE code,
+        not mapped: on an invalid frame the loop would encode ``fill_value * scale[k]`` per
+        channel, so the bytes are the loop's on filled samples when that is one code for
+        every channel -- a `fill_value` of 0, the usual case.
+
         A read in every respect but the decoding: a damaged file is repaired under
         ``verify='fix'`` as ``read(count)`` repairs it (the frames are located and the
         whole request is answered through that index), and ``verify=True`` raises what
@@ -399,6 +425,7 @@ class PackedBytesMixin:
             raise ValueError("read_packed: payloads are whole 32-bit words")
         payload_out = samples_per_frame * chunk_out * bps_out // 8
         recode = requant and (nthread != g.nslot or chunk_out != g.chunk)
+        gains = None if scale is None or np.ndim(scale) == 0 else self._component_gains(scale, g)
         if recode:
             if not regroup:
                 raise NotImplementedError(
@@ -408,6 +435,14 @@ class PackedBytesMixin:
                 raise NotImplementedError(
                     "read_packed: a change of sample width or scale keeps the number of components ({} x {} codes "
                     "-> {} x {})".format(g.nslot, g.chunk, nthread, chunk_out))
+        if gains is not None:
+            if not kernels.recode_tables_supported(g.bps, bps_out, g.chunk, g.nslot, chunk_out, nthread,
+                                                   g.payload_nbytes, payload_out):
+                raise NotImplementedError(
+                    "read_packed: {} x {} codes of {} bits -> {} x {} codes of {} bits is not a conversion the "
+                    "recode kernel with a table per component takes".format(g.nslot, g.chunk, g.bps, nthread,
+                                                                            chunk_out, bps_out))
+        elif recode:
             if not kernels.recode_supported(g.bps, bps_out, g.chunk, g.nslot, chunk_out, nthread,
                                             g.payload_nbytes, payload_out):
                 raise NotImplementedError(
@@ -428,7 +463,10 @@ class PackedBytesMixin:
             raise ValueError("read_packed: whole bytes only: seek to a multiple of {} samples".format(whole))
         kernels.require_gpu()
         nout = count // samples_per_frame
-        table = kernels.requant_table(g.coder, g.bps, coder, bps_out, scale) if requant else None
+        if gains is not None:                               # (uploaded once, for every window of the walk)
+            table = torch.from_numpy(kernels.requant_tables(g.coder, g.bps, coder, bps_out, gains)).cuda()
+        else:
+            table = kernels.requant_table(g.coder, g.bps, coder, bps_out, scale) if requant else None
         if count == 0:
             return torch.empty((0, nthread, payload_out), dtype=torch.uint8, device='cuda'), np.ones(0, bool)
 
@@ -439,7 +477,11 @@ class PackedBytesMixin:
             marks = _ValidityMarks(nout, samples_per_frame, start, stop, self.samples_per_frame, g.nslot)
 
             def visit(dbuf, src, s, e, row_lo, row_hi, first_row):
-                if recode:
+                if gains is not None:
+                    kernels.recode_frames_tables(dbuf, e - s, g.payload_nbytes, g.bps, g.chunk, g.nslot, bps_out,
+                                                 chunk_out, nthread, payload_out, table, fill_code=fill_code, src=src,
+                                                 row_lo=row_lo, row_hi=row_hi, first_row=first_row, out=out.reshape(-1))
+                elif recode:
                     kernels.recode_frames(dbuf, e - s, g.payload_nbytes, g.bps, g.chunk, g.nslot, bps_out, chunk_out,
                                           nthread, payload_out, table, fill_code=fill_code, src=src, row_lo=row_lo,
                                           row_hi=row_hi, first_row=first_row, out=out.reshape(-1))

@@ -1,5 +1,5 @@
 // The packed-byte entries of bbdecode.hip (bb_count_states, bb_count_states_bins, bb_repack_frames,
-// bb_requant_frames, bb_recode_frames), their argument checks and what they share.  The ORDER of the checks is part of
+// bb_requant_frames, bb_recode_frames, bb_recode_frames_tables), their argument checks and what they share.  The ORDER of the checks is part of
 // the ABI: tests/golden/abi_return_codes.json holds it in place.
 extern "C++" { namespace {                                   // (the entries have C linkage: the include stands among them)
 // A slot's stream of rows: payloads of whole dwords that hold whole rows of `chunk` codes
@@ -68,6 +68,11 @@ inline uint64_t even_pieces(uint64_t payload, uint64_t seg_max, uint32_t *seg_by
 inline uint32_t fill_word(int fill_code, int bps) { return (uint32_t)fill_code * (0xffffffffu / ((1u << bps) - 1u)); }
 #define BB_WAVE_ITEM_GRID 4096ull                    // workgroups: several rounds of what 256 CUs hold (repack: 4 each, 37 KiB of LDS)
 inline dim3 wave_grid(uint64_t nwork) { return capped_grid((nwork + BB_WAVES_PER_BLOCK - 1) / BB_WAVES_PER_BLOCK, BB_WAVE_ITEM_GRID); }
+// ... of k_recode_tables, whose LDS depends on the launch: the same four rounds of what 256 CUs hold, 160 KiB and at most 8 workgroups each
+inline dim3 tables_grid(uint64_t nwork, size_t lds)
+{
+    return capped_grid((nwork + BB_WAVES_PER_BLOCK - 1) / BB_WAVES_PER_BLOCK, 4ull * 256ull * std::min<uint64_t>(8, (160ull << 10) / lds));
+}
 } }
 
 // ---- sampler statistics (k_states.h).  EXTENSION: no reference counterpart. ----
@@ -354,17 +359,20 @@ static int recode_params_check(const bb_recode_params *p, uint64_t *R_in, uint64
 
 int bb_recode_check(const bb_recode_params *p) { uint64_t R_in, R_out; return recode_params_check(p, &R_in, &R_out); }
 
-int bb_recode_frames(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size_t nframes,
-                     const bb_recode_params *p, void *d_out, size_t out_nbytes, void *stream)
+// What both recode entries do after the parameter check: the output and source checks of bb_recode_frames,
+// in its order, and the members every recode kernel's arguments share.  a.nwork == 0: nothing is asked for.
+extern "C++" { namespace {
+template <class Args>
+inline int recode_args(Args &a, const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size_t nframes,
+                       const bb_recode_params *p, uint64_t R_in, uint64_t R_out, void *d_out, size_t out_nbytes,
+                       uint32_t item_bits)
 {
-    uint64_t R_in, R_out; packed_out o;
-    int rc = recode_params_check(p, &R_in, &R_out);
-    if (rc) return rc;
+    packed_out o;
+    a.nwork = 0;
     const uint64_t bi = (uint64_t)p->chunk_in * (uint64_t)p->bps_in, bo = (uint64_t)p->chunk_out * (uint64_t)p->bps_out;   // bits per row and slot
-    rc = packed_output(d_out, out_nbytes, nframes, p->payload_in, R_in, R_out, p->payload_out, (uint64_t)p->nslot_out, bi, bo,
-                       p->row_lo, p->row_hi, p->first_row, &o);
+    int rc = packed_output(d_out, out_nbytes, nframes, p->payload_in, R_in, R_out, p->payload_out, (uint64_t)p->nslot_out, bi, bo,
+                           p->row_lo, p->row_hi, p->first_row, &o);
     if (rc || !o.nrows) return rc;
-    bb_recode_args a;
     rc = packed_source(a, d_buf, buf_nbytes, d_src, p->src0, p->src_stride,
                        (uint64_t)nframes * (uint64_t)p->nslot_in, p->payload_in);
     if (rc) return rc;
@@ -377,20 +385,64 @@ int bb_recode_frames(const void *d_buf, size_t buf_nbytes, const int64_t *d_src,
     a.nslot_in = (uint32_t)p->nslot_in; a.nslot_out = (uint32_t)p->nslot_out;
     a.lbi = ceil_log2(bi); a.lbo = ceil_log2(bo);
     a.lpi = (uint32_t)log2_bps(p->bps_in); a.lpo = (uint32_t)log2_bps(p->bps_out);
-    // the wider side of an item is 8 KiB; at least 256 rows: 32 bytes or more of every slot on either side
-    a.T = BB_RECODE_ITEM_BITS / ((uint32_t)p->nslot_in * (uint32_t)p->chunk_in * (uint32_t)std::max(p->bps_in, p->bps_out));
+    // the wider side of an item is item_bits (k_recode: 8 KiB; at least 256 rows: 32 bytes or more of every slot on either side)
+    a.T = item_bits / ((uint32_t)p->nslot_in * (uint32_t)p->chunk_in * (uint32_t)std::max(p->bps_in, p->bps_out));
     a.sstride = ((a.T << a.lbi) >> 3) + BB_REPACK_SLACK;
     a.nseg = (R_out + a.T - 1) / a.T;
     const uint64_t nf = o.f_last - a.F0 + 1;
     if (nf > (~0ull) / a.nseg) return BB_ERANGE;
-    a.nwork = nf * a.nseg;
     // the codes that stay adjacent on both sides, as far as a dword of either side holds them
     a.lgc = std::min(std::min(ceil_log2((uint32_t)p->chunk_in), ceil_log2((uint32_t)p->chunk_out)), std::min(5u - a.lpi, 5u - a.lpo));
     a.fill = (uint32_t)p->fill_code;
+    a.nwork = nf * a.nseg;
+    return BB_OK;
+}
+} }
+
+int bb_recode_frames(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size_t nframes,
+                     const bb_recode_params *p, void *d_out, size_t out_nbytes, void *stream)
+{
+    uint64_t R_in, R_out;
+    int rc = recode_params_check(p, &R_in, &R_out);
+    if (rc) return rc;
+    bb_recode_args a;
+    rc = recode_args(a, d_buf, buf_nbytes, d_src, nframes, p, R_in, R_out, d_out, out_nbytes, BB_RECODE_ITEM_BITS);
+    if (rc || !a.nwork) return rc;
     uint8_t *m = reinterpret_cast<uint8_t *>(a.map);                          // (entries the input cannot have: 0)
     for (int c = 0; c < 256; ++c) m[c] = c < (1 << p->bps_in) ? p->map[c] : 0;
     const dim3 grid = wave_grid(a.nwork);
     hipLaunchKernelGGL(k_recode, grid, dim3(BB_BLOCK), 0, (hipStream_t)stream, a);
+    BB_HIP(hipGetLastError());
+    return BB_OK;
+}
+
+// ---- ... with one table per component of a row (k_recode_tables.h): a gain per (thread, channel).  The parameter
+//      block and its check are bb_recode_frames'; the block's own map is checked as there and not used. ----
+int bb_recode_tables_check(const bb_recode_params *p) { uint64_t R_in, R_out; return recode_params_check(p, &R_in, &R_out); }
+
+int bb_recode_frames_tables(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size_t nframes,
+                            const bb_recode_params *p, const uint8_t *d_tables, size_t tables_nbytes,
+                            void *d_out, size_t out_nbytes, void *stream)
+{
+    uint64_t R_in, R_out;
+    int rc = recode_params_check(p, &R_in, &R_out);
+    if (rc) return rc;
+    bb_recode_tables_args a;
+    // items of 4 KiB on the wider side where the input is it, of 8 KiB where the output is wider (DESIGN.md 3.12:
+    // measured); at least 128 rows: 16 bytes or more of every slot on either side
+    const uint32_t item_bits = p->bps_in >= p->bps_out ? BB_RECODE_ITEM_BITS / 2 : BB_RECODE_ITEM_BITS;
+    rc = recode_args(a, d_buf, buf_nbytes, d_src, nframes, p, R_in, R_out, d_out, out_nbytes, item_bits);
+    if (rc || !a.nwork) return rc;
+    if (!d_tables || ((uintptr_t)d_tables & 3)) return BB_EINVAL;
+    a.tab_n = ((uint32_t)p->nslot_in * (uint32_t)p->chunk_in) << p->bps_in;   // at most 8 KiB (recode_params_check)
+    if (tables_nbytes < a.tab_n) return BB_ERANGE;
+    a.tables = d_tables;
+    a.tab_lds = (a.tab_n + 255u) & ~255u;
+    a.in_lds = bb_recode_tables_lds(item_bits);
+    a.ok_words = bb_recode_tables_flat(item_bits) / 4u / 32u;
+    const size_t lds = a.tab_lds + (size_t)BB_WAVES_PER_BLOCK * (a.in_lds + 4u * a.ok_words);   // 22 .. 46 KiB
+    const dim3 grid = tables_grid(a.nwork, lds);
+    hipLaunchKernelGGL(k_recode_tables, grid, dim3(BB_BLOCK), lds, (hipStream_t)stream, a);
     BB_HIP(hipGetLastError());
     return BB_OK;
 }

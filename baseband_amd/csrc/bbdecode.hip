@@ -17,6 +17,7 @@
 #include "k_repack.h"
 #include "k_requant.h"
 #include "k_recode.h"
+#include "k_recode_tables.h"
 #include "k_tfpick.h"
 #if BB_EXP
 #include "k_burst.h"
@@ -999,8 +1000,8 @@ int bb_build_index(const bb_frame_rec *d_recs, size_t nrecs,
     if (nrecs == 0) return BB_OK;
     dim3 grid;
     if (int rc = record_grid(nrecs, BB_BLOCK, &grid)) return rc;
-    hipLaunchKernelGGL(k_build_index, grid, dim3(BB_BLOCK), 0, st,
-                       d_recs, (uint64_t)nrecs, d_thread_slot, nslot, d_src, (uint64_t)nframes_out);
+    hipLaunchKernelGGL(k_index_verify, grid, dim3(BB_BLOCK), 0, st, d_recs, (uint64_t)nrecs, d_thread_slot, nslot,
+                       d_src, (uint64_t)nframes_out, 1u, (uint64_t)0, (uint32_t *)nullptr);    // (nothing verified: the scatter alone)
     BB_HIP(hipGetLastError());
     return BB_OK;
 }

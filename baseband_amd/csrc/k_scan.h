@@ -523,9 +523,12 @@ void k_verify_records(const bb_frame_rec *recs, uint64_t nrecs, int32_t first_in
     if (bb_lane() == 0 && m) atomicAdd(nbad, (uint32_t)__popcll(m));
 }
 
-// k_build_index and k_verify_records in ONE launch (the read_window entry points:
-// a mid-size read is five launches otherwise, and the three small ones between two
-// decodes cost 20-30 us of a 650 us read; round 4).  `nbad` may be null.
+// The index and k_verify_records in ONE launch (the read_window entry points: a mid-size
+// read is five launches otherwise, and the three small ones between two decodes cost 20-30 us
+// of a 650 us read; round 4): the records of valid frames in place are scattered into the dense
+// output-ordered source table, which the caller's launch wrapper pre-fills with -1.  `nbad` may
+// be null: the scatter alone, which is bb_build_index (it had a kernel of its own with these
+// very conditions until the code object's count of kernels needed the place).
 __global__ __launch_bounds__(BB_BLOCK)
 void k_index_verify(const bb_frame_rec *recs, uint64_t nrecs, const int16_t *thread_slot, int nslot,
                     int64_t *src, uint64_t nframes_out, uint32_t recs_per_index, uint64_t nstrict, uint32_t *nbad)
@@ -550,27 +553,4 @@ void k_index_verify(const bb_frame_rec *recs, uint64_t nrecs, const int16_t *thr
         const unsigned long long m = __ballot(bad);
         if (bb_lane() == 0 && m) atomicAdd(nbad, (uint32_t)__popcll(m));
     }
-}
-
-// Scatter scan records into the dense output-ordered source table (which the
-// caller's launch wrapper pre-fills with -1).
-__global__ __launch_bounds__(BB_BLOCK)
-void k_build_index(const bb_frame_rec *recs, uint64_t nrecs,
-                   const int16_t *thread_slot, int nslot,
-                   int64_t *src, uint64_t nframes_out)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * BB_BLOCK + threadIdx.x;
-    if (i >= nrecs) return;
-    const bb_u4 raw = *reinterpret_cast<const bb_u4 *>(&recs[i]);
-    bb_frame_rec r;
-    *reinterpret_cast<bb_u4 *>(&r) = raw;
-    if (!(r.flags & BB_FRAME_OK)) return;
-    if (r.time_index < 0 || (uint64_t)r.time_index >= nframes_out) return;
-    int slot = 0;
-    if (thread_slot) {
-        slot = thread_slot[r.thread_id & 0x3ff];
-        if (slot < 0 || slot >= nslot) return;
-    }
-    if (r.flags & BB_FRAME_INVALID) return;             // stays -1 -> fill
-    src[(uint64_t)r.time_index * nslot + slot] = r.payload_offset;
 }

@@ -559,7 +559,7 @@ STATES_MAX_ROW_BITS = 128      # chunk * bps the counting kernel takes (16 byte 
 
 
 # -- what the calls on packed bytes share (count_states, count_states_bins, repack_frames, requant_frames,
-#    recode_frames)
+#    recode_frames, recode_frames_tables)
 def _default_payload(bps, chunk):
     """The smallest payload of whole dwords and rows: what `*_supported` asks about by default."""
     return max(4, chunk * bps // 8) if bps in (1, 2, 4, 8) and chunk > 0 else 4
@@ -763,6 +763,78 @@ def recode_frames(dbuf, nframes, payload_in, bps_in, chunk_in, nslot_in, bps_out
     p = _lib.recode_params(bps_in, bps_out, chunk_in, nslot_in, chunk_out, nslot_out, payload_in, payload_out, table,
                            fill_code, src0, src_stride, row_lo, row_hi, first_row)
     return _frames_out(lib.bb_recode_frames, lib.bb_recode_check, 'bb_recode_frames', dbuf, src, nframes, p,
+                       first_row + row_hi - row_lo, payload_out, bps_out * chunk_out, nslot_out, out)
+
+
+def requant_tables(coder_in, bps_in, coder_out, bps_out, scales):
+    """The tables of `recode_frames_tables` that are decode, times ``scales[k]``, encode for
+    component k of a row: uint8 NumPy array of shape ``(ncomp, 1 << bps_in)``, row k of which is
+    ``requant_table(coder_in, bps_in, coder_out, bps_out, scales[k])``.  Made as that one is --
+    the decoder's float32 levels, a float32 product with ``np.float32(scales[k])``, ONE
+    `encode_flat` call for all rows -- so it IS the arithmetic of the loop
+    ``fw.write(fr.read(n) * gains)``."""
+    scales = np.asarray(scales, dtype=np.float32).reshape(-1)
+    if scales.size == 0 or not np.isfinite(scales).all():
+        raise ValueError("requant_tables: scales must be finite, one per component")
+    levels = _lib.get_levels(coder_in, bps_in).astype(np.float32)
+    levels = (levels[None, :] * scales[:, None]).reshape(-1)
+    levels = np.pad(levels, (0, -levels.size % 8))              # (whole bytes at every width the encoder has)
+    packed = encode_flat(torch.from_numpy(levels).cuda(), coder_out, bps_out).cpu().numpy()
+    codes = (packed[:, None] >> np.arange(0, 8, bps_out, dtype=np.uint8)) & ((1 << bps_out) - 1)
+    return np.ascontiguousarray(codes.reshape(-1)[:scales.size << bps_in].astype(np.uint8).reshape(scales.size, 1 << bps_in))
+
+
+def recode_tables_supported(bps_in, bps_out, chunk_in, nslot_in, chunk_out, nslot_out, payload_in=None,
+                            payload_out=None):
+    """Would `recode_frames_tables` take these widths and this geometry (equal thread structures
+    included)?  (bb_recode_tables_check; no device needed.)"""
+    if payload_in is None:
+        payload_in = _default_payload(bps_in, chunk_in)
+    if payload_out is None:
+        payload_out = _default_payload(bps_out, chunk_out)
+    return _lib.recode_tables_check(bps_in, bps_out, chunk_in, nslot_in, chunk_out, nslot_out,
+                                    payload_in, payload_out) == _lib.BB_OK
+
+
+def _device_tables(tables, ncomp, bps_in, bps_out, device):
+    """`tables` of `recode_frames_tables` -> a contiguous uint8 device tensor of ``(ncomp, 1 << bps_in)``.  A NumPy
+    array is checked against ``1 << bps_out`` here and uploaded; a device tensor's values are the kernel's to mask."""
+    shape = (ncomp, 1 << bps_in) if bps_in in (1, 2, 4, 8) else None
+    if isinstance(tables, np.ndarray):
+        if tables.dtype != np.uint8 or (shape is not None and tables.shape != shape):
+            raise ValueError("recode_frames_tables: tables must be a uint8 array of shape {}, not {} of shape {}"
+                             .format(shape, tables.dtype, tables.shape))
+        if bps_out in (1, 2, 4, 8) and tables.size and int(tables.max()) >= 1 << bps_out:
+            raise ValueError("recode_frames_tables: a table entry is not a code of {} bits".format(bps_out))
+        return torch.from_numpy(np.ascontiguousarray(tables)).to(device)
+    if not torch.is_tensor(tables) or tables.dtype != torch.uint8 or not tables.is_contiguous() or \
+            tables.device != device or (shape is not None and tuple(tables.shape) != shape):
+        raise ValueError("recode_frames_tables: tables must be a contiguous uint8 array or device tensor of shape {}"
+                         .format(shape))
+    return tables
+
+
+def recode_frames_tables(dbuf, nframes, payload_in, bps_in, chunk_in, nslot_in, bps_out, chunk_out, nslot_out,
+                         payload_out, tables, fill_code=0, src=None, src0=0, src_stride=0, row_lo=0, row_hi=None,
+                         first_row=0, out=None):
+    """`recode_frames` with one table per component of a row (bb_recode_frames_tables): code c of
+    component k = s * chunk_in + p becomes ``tables[k][c]``; everything else -- rows, index,
+    `fill_code` (one code, not mapped), `out`, whole bytes -- is as there, and the thread
+    structures may be equal.  `tables`: uint8 of shape ``(nslot_in * chunk_in, 1 << bps_in)``
+    (`requant_tables`), a NumPy array (checked against ``1 << bps_out`` and uploaded once per
+    call) or a device tensor (the kernel keeps the low `bps_out` bits of every entry).  Nothing
+    is decoded and nothing synchronises."""
+    if row_hi is None:
+        row_hi = _all_rows(nframes, payload_in, bps_in, chunk_in)
+    p = _lib.recode_params(bps_in, bps_out, chunk_in, nslot_in, chunk_out, nslot_out, payload_in, payload_out, (),
+                           fill_code, src0, src_stride, row_lo, row_hi, first_row)
+    check(lib.bb_recode_tables_check(C.byref(p)), 'bb_recode_frames_tables')    # (before a shape is made of the parameters)
+    dtab = _device_tables(tables, nslot_in * chunk_in, bps_in, bps_out, dbuf.device)
+
+    def call(buf, buf_n, src_, nfr, params, out_, out_n, stream):
+        return lib.bb_recode_frames_tables(buf, buf_n, src_, nfr, params, _ptr(dtab), dtab.numel(), out_, out_n, stream)
+
+    return _frames_out(call, lib.bb_recode_tables_check, 'bb_recode_frames_tables', dbuf, src, nframes, p,
                        first_row + row_hi - row_lo, payload_out, bps_out * chunk_out, nslot_out, out)
 
 

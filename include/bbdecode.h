@@ -910,6 +910,35 @@ int bb_recode_frames(const void *d_buf, size_t buf_nbytes,
                      void *d_out, size_t out_nbytes, void *stream);
 int bb_recode_check(const bb_recode_params *params);
 
+/*
+ * bb_recode_frames with ONE TABLE PER COMPONENT of a row: a gain per (thread,
+ * channel) in front of the requantizer.  Everything is as for bb_recode_frames
+ * -- the same parameter block, geometry, limits and whole-byte rule; equal
+ * thread structures on both sides are a legal geometry -- but the output field
+ * of component k = s * chunk_in + p is
+ *     d_tables[(k << bps_in) + c]
+ * or fill_code (not mapped) where the source counts nothing.  d_tables is
+ * DEVICE memory on a 4-byte boundary: ncomp << bps_in bytes (ncomp = nslot_in *
+ * chunk_in; at most 8 KiB), one table of 1 << bps_in output codes after the
+ * other.  The host cannot see the values, so the kernel keeps the low bps_out
+ * bits of every table byte: a bad table never sets bits of a neighbouring
+ * field.  The block's own map is checked as bb_recode_check checks it and is
+ * otherwise ignored; leave it zero.
+ *
+ * Checks: everything bb_recode_frames checks, in its order (a request of no
+ * rows is BB_OK there and then); then d_tables NULL or not 4-byte aligned
+ * (BB_EINVAL); then tables_nbytes < ncomp << bps_in (BB_ERANGE).
+ * Stream-ordered, never allocates, never synchronises; nframes == 0 or row_lo
+ * == row_hi launches nothing; an argument error leaves d_out untouched.
+ * bb_recode_tables_check answers what bb_recode_check answers.
+ */
+int bb_recode_frames_tables(const void *d_buf, size_t buf_nbytes,
+                            const int64_t *d_src, size_t nframes,
+                            const bb_recode_params *params,
+                            const uint8_t *d_tables, size_t tables_nbytes,
+                            void *d_out, size_t out_nbytes, void *stream);
+int bb_recode_tables_check(const bb_recode_params *params);
+
 /* ---- byte-aligned formats with an axis permutation --------------------- */
 
 /*
