@@ -126,6 +126,13 @@ class StatesParams(C.Structure):
                 ('row_lo', C.c_uint64), ('row_hi', C.c_uint64)]
 
 
+class MomentsParams(C.Structure):
+    _fields_ = [('layout', C.c_int32), ('npol', C.c_int32), ('nchan', C.c_int32), ('ncomp', C.c_int32),
+                ('ntime', C.c_uint64), ('t_lo', C.c_uint64), ('t_hi', C.c_uint64),
+                ('src0', C.c_int64), ('src_stride', C.c_int64),
+                ('bin_rows', C.c_uint64), ('first_row', C.c_uint64), ('nbins', C.c_uint64)]
+
+
 class RepackParams(C.Structure):
     _fields_ = [('bps', C.c_int32), ('coder_in', C.c_int32), ('coder_out', C.c_int32),
                 ('chunk_in', C.c_int32), ('nslot_in', C.c_int32), ('chunk_out', C.c_int32),
@@ -196,6 +203,12 @@ LAYOUT_GUPPI_CF = 0
 LAYOUT_MKBF = 1
 LAYOUT_GUPPI_TF = 2
 
+# enum bb_moments_layout (bb_i8_moments; not the layouts of bb_decode_i8_tiled)
+MOMENTS_GUPPI_CF = 0
+MOMENTS_GUPPI_TF = 1
+MOMENTS_ROWS = 2
+MOMENTS_MKBF = 3
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -243,6 +256,8 @@ SIGNATURES = [
     ('bb_count_states_bins', C.c_int, [_vp, _sz, _vp, _sz, C.POINTER(StatesParams), C.c_uint64, C.c_uint64,
                                        C.c_uint64, _vp, _sz, _vp]),
     ('bb_count_states_bins_check', C.c_int, [C.POINTER(StatesParams), C.c_uint64]),
+    ('bb_i8_moments', C.c_int, [_vp, _sz, _vp, _sz, C.POINTER(MomentsParams), _vp, _sz, _vp]),
+    ('bb_i8_moments_check', C.c_int, [C.POINTER(MomentsParams)]),
     ('bb_repack_frames', C.c_int, [_vp, _sz, _vp, _sz, C.POINTER(RepackParams), _vp, _sz, _vp]),
     ('bb_repack_check', C.c_int, [C.POINTER(RepackParams)]),
     ('bb_requant_frames', C.c_int, [_vp, _sz, _vp, _sz, C.POINTER(RequantParams), _vp, _sz, _vp]),
@@ -340,6 +355,23 @@ def count_states_bins_check(bps, chunk=1, bin_rows=8, nslot=1, payload_nbytes=4,
     it (bb_count_states_bins_check: no buffers, no device): BB_OK, BB_EINVAL or BB_ENOTSUP."""
     p = states_params(bps, chunk, nslot, payload_nbytes, 0, 0, row_lo, row_hi, reserved)
     return lib.bb_count_states_bins_check(C.byref(p), bin_rows)
+
+
+def moments_params(layout, npol, nchan, ncomp, ntime, t_lo=0, t_hi=0, bin_rows=1, nbins=0, first_row=0,
+                   src0=0, src_stride=0):
+    p = MomentsParams()
+    p.layout, p.npol, p.nchan, p.ncomp = layout, npol, nchan, ncomp
+    p.ntime, p.t_lo, p.t_hi = ntime, t_lo, t_hi
+    p.src0, p.src_stride = src0, src_stride
+    p.bin_rows, p.first_row, p.nbins = bin_rows, first_row, nbins
+    return p
+
+
+def i8_moments_check(layout, npol, nchan, ncomp, ntime, t_lo=0, t_hi=0, bin_rows=1, src0=0, src_stride=0):
+    """What `bb_i8_moments` would answer to these parameters, as far as they decide it
+    (bb_i8_moments_check: no buffers, no device): BB_OK, BB_EINVAL or BB_ENOTSUP."""
+    p = moments_params(layout, npol, nchan, ncomp, ntime, t_lo, t_hi, bin_rows, 0, 0, src0, src_stride)
+    return lib.bb_i8_moments_check(C.byref(p))
 
 
 def repack_params(bps, coder_in, coder_out, chunk_in, nslot_in, chunk_out, nslot_out, payload_in, payload_out,

@@ -7,13 +7,15 @@ loop would take them (base/base.py:957-967 with the per-format ``_get_frame``
 rules).  Runs of frames with the same row range are staged frame-by-frame
 through the pinned pipeline and decoded by one kernel launch per window.
 """
+import operator
+
 import numpy as np
 import torch
 
 from .. import kernels
 from ..placement import empty_output
 from ..staging import WindowPipeline
-from .base import GPUStreamReaderBase, _to_host_array
+from .base import GPUStreamReaderBase, _apply_squeeze, _to_host_array
 
 
 class BlockStreamReader(GPUStreamReaderBase):
@@ -320,3 +322,171 @@ class BlockStreamReader(GPUStreamReaderBase):
         else:
             _to_host_array(data, out)
         return out
+
+    # -- power and moments per channel and time bin from the stored int8 bytes (kernels.i8_moments)
+    moments_fallback_bytes = 256 << 20      # decoded bytes per piece of the fallback (read, then reduce)
+
+    def _moments_geometry(self):
+        """``(layout, ncomp)`` of the stored int8 samples for `kernels.i8_moments`
+        (``_lib.MOMENTS_*``), or a str: why the kernel does not take this stream."""
+        return "{} has no kernel for its stored samples".format(type(self).__name__)
+
+    def _moments_ntime(self, frame):
+        """Times stored in the payload of `frame`."""
+        return self.samples_per_frame
+
+    def _moments_plan(self, bin_samples):
+        """``(layout, npol, nchan, ncomp)`` where the kernel takes this stream with bins of
+        `bin_samples`, else the reason as a str."""
+        geom = self._moments_geometry()
+        if isinstance(geom, str):
+            return geom
+        layout, ncomp = geom
+        npol, nchan = self._unsliced_shape
+        ntimes = {self._moments_ntime(0), self._moments_ntime(self._nframes - 1)}
+        for ntime in ntimes:
+            if not kernels.i8_moments_supported(layout, npol, nchan, ncomp, ntime, bin_rows=bin_samples,
+                                                src0=self._header_nbytes, src_stride=self._frame_nbytes):
+                return ("the moments kernel does not take {} pol x {} chan x {} components, {} times a frame, "
+                        "payloads at {} + k * {} bytes".format(npol, nchan, ncomp, ntime, self._header_nbytes,
+                                                               self._frame_nbytes))
+        return layout, npol, nchan, ncomp
+
+    def moment_series(self, bin_samples, count=None, packed=None):
+        """Sum of x and sum of x * x of every real component per time bin, over the samples
+        ``read(count)`` would return from the current offset -> int64 device tensor of shape
+        ``(nbins,) + sample_shape + ((2,) if complex) + (2,)`` with ``nbins = ceil(count /
+        bin_samples)``; the last axis is (sum x, sum x * x), the one before it (real,
+        imaginary).  Bin ``b`` covers the samples ``[offset + b * bin_samples, offset + (b + 1)
+        * bin_samples)`` (the last bin may be short).  The offset does not move.
+
+        With ``packed=None`` the sums come from the stored int8 bytes where the kernel takes the
+        stream (bb_i8_moments: one pass over the file's bytes, nothing is decoded, every stored
+        channel summed; `squeeze` and `subset` are applied to the small result as ``read()``
+        applies them to a sample) and from ``read()`` in pieces followed by a reduction
+        elsewhere (MKBF heaps, real GUPPI samples, samples of 6 bytes, payloads off a dword);
+        both are exact.  ``packed=False`` always reads and reduces, ``packed=True`` raises
+        `NotImplementedError` where the kernel does not take the stream."""
+        if self.closed:
+            raise ValueError("I/O operation on closed stream.")
+        bin_samples = operator.index(bin_samples)
+        if bin_samples < 1:
+            raise ValueError("moment_series: bin_samples must be at least 1")
+        if self.bps != 8:
+            raise NotImplementedError("moment_series: samples of {} bits are not int8".format(self.bps))
+        left = self.shape[0] - self.offset
+        if count is None or count < 0:
+            count = max(0, left)
+        if count > left:
+            raise EOFError("cannot read from beyond end of input.")
+        kernels.require_gpu()
+        nbins = -(-count // bin_samples)
+        plan = None if packed is False else self._moments_plan(bin_samples)
+        if isinstance(plan, str):
+            if packed:
+                raise NotImplementedError("moment_series: " + plan)
+            plan = None
+        if plan is None:
+            return self._moments_by_read(bin_samples, count, nbins)
+        layout, npol, nchan, ncomp = plan
+        sums = torch.zeros((nbins, npol, nchan, ncomp, 2), dtype=torch.int64, device='cuda')
+        # runs of frames that share a row range and a payload size: one launch each (per window)
+        runs = []
+        for f, a, b in self._pieces(self.offset, count):
+            nt = self._moments_ntime(f)
+            if runs and runs[-1][1] == f and tuple(runs[-1][2:]) == (a, b, nt):
+                runs[-1][1] = f + 1
+            else:
+                runs.append([f, f + 1, a, b, nt])
+        image = self._image()
+        resident = self._resident_bytes()
+        done = 0
+
+        def add(dbuf, nframes, a, b, nt, first_row):
+            kernels.i8_moments(dbuf, nframes, layout, npol, nchan, ncomp, nt, a, b, bin_samples, nbins,
+                               first_row=first_row, src0=self._header_nbytes, src_stride=self._frame_nbytes, sums=sums)
+
+        for f0, f1, a, b, nt in runs:
+            if resident is not None:
+                lo = self._frame_span(f0)[0]
+                last_lo, last_n = self._frame_span(f1 - 1)
+                add(self._device_window(resident, lo, min(last_lo + last_n, resident.numel())), f1 - f0, a, b, nt, done)
+            elif f1 == f0 + 1 and self._ahead is not None and self._ahead[0] == f0:
+                add(self._ahead[1], 1, a, b, nt, done)      # the frame that small reads keep staged
+            else:
+                nbytes = self._frame_span(f0)[1]
+                per_win = max(1, self.window_bytes // self._frame_nbytes)
+                cap = max(per_win * self._frame_nbytes, nbytes)
+                if self._pipeline is None or self._pipeline.cap < cap:
+                    self._pipeline = WindowPipeline(image, cap)
+                ranges, spans = [], []
+                for s in range(f0, f1, per_win):
+                    e = min(f1, s + per_win)
+                    lo = self._frame_span(s)[0]
+                    last_lo, last_n = self._frame_span(e - 1)
+                    ranges.append((lo, min(last_lo + last_n, len(image))))
+                    spans.append((s, e))
+
+                def process(dbuf, i, base=done, a=a, b=b, nt=nt, f0=f0):
+                    s, e = spans[i]
+                    add(dbuf, e - s, a, b, nt, base + (s - f0) * (b - a))
+
+                self._pipeline.run(ranges, process)
+            done += (f1 - f0) * (b - a)
+        assert done == count
+        if ncomp == 1:
+            sums = sums.reshape(nbins, npol, nchan, 2)
+        # squeeze and subset, as read() applies them to a sample
+        if self.squeeze:
+            sums = sums.reshape((nbins,) + _apply_squeeze((npol, nchan)) + tuple(sums.shape[3:]))
+        if self.subset:
+            sums = sums[(slice(None),) + self._torch_subset()]
+        return sums
+
+    def _moments_by_read(self, bin_samples, count, nbins):
+        """`moment_series` from ``read()`` in pieces of at most `moments_fallback_bytes` of
+        decoded samples, summed in int64 (exact: the decoded values are the stored integers)."""
+        comp = (2,) if self.complex_data else ()
+        sums = torch.zeros((nbins,) + tuple(self.sample_shape) + comp + (2,), dtype=torch.int64, device='cuda')
+        per_sample = 4 * max(1, int(np.prod(self.sample_shape))) * (2 if self.complex_data else 1)
+        step = max(1, self.moments_fallback_bytes // per_sample)
+        offset, host = self.offset, self.host_results
+        self.host_results = False
+        try:
+            for lo in range(0, count, step):
+                n = min(step, count - lo)
+                data = self.read(n)
+                x = (torch.view_as_real(data) if self.complex_data else data).to(torch.int64)
+                del data
+                x = torch.stack((x, x * x), -1)
+                # the rows up to the next bin edge, whole bins, the rest
+                head = min(n, -lo % bin_samples)
+                whole = (n - head) // bin_samples
+                b = (lo + head) // bin_samples
+                if head:
+                    sums[lo // bin_samples] += x[:head].sum(0)
+                if whole:
+                    sums[b:b + whole] += x[head:head + whole * bin_samples].reshape(
+                        (whole, bin_samples) + tuple(x.shape[1:])).sum(1)
+                if head + whole * bin_samples < n:
+                    sums[b + whole] += x[head + whole * bin_samples:].sum(0)
+        finally:
+            self.offset, self.host_results = offset, host
+        return sums
+
+    def power_series(self, bin_samples, count=None, packed=None):
+        """Mean ``|x|**2`` per sample and time bin, from `moment_series`: float64 device tensor
+        of shape ``(nbins,) + sample_shape``: the sum of x * x over the components of a bin,
+        divided by the number of samples in it.  Name and meaning are those of the VDIF and
+        Mark 5B method; `packed` as in `moment_series`."""
+        m = self.moment_series(bin_samples, count, packed)
+        nbins = m.shape[0]
+        left = self.shape[0] - self.offset
+        count = max(0, left) if count is None or count < 0 else count
+        sq = m[..., 1]
+        if self.complex_data:
+            sq = sq.sum(-1)
+        n = torch.full((nbins,), operator.index(bin_samples), dtype=torch.int64, device=m.device)
+        if nbins:
+            n[-1] = count - (nbins - 1) * operator.index(bin_samples)
+        return sq.double() / n.double().reshape((nbins,) + (1,) * (sq.dim() - 1))

@@ -1,5 +1,5 @@
 // The packed-byte entries of bbdecode.hip (bb_count_states, bb_count_states_bins, bb_repack_frames,
-// bb_requant_frames, bb_recode_frames, bb_recode_frames_tables), their argument checks and what they share.  The ORDER of the checks is part of
+// bb_requant_frames, bb_recode_frames, bb_recode_frames_tables, bb_i8_moments), their argument checks and what they share.  The ORDER of the checks is part of
 // the ABI: tests/golden/abi_return_codes.json holds it in place.
 extern "C++" { namespace {                                   // (the entries have C linkage: the include stands among them)
 // A slot's stream of rows: payloads of whole dwords that hold whole rows of `chunk` codes
@@ -443,6 +443,102 @@ int bb_recode_frames_tables(const void *d_buf, size_t buf_nbytes, const int64_t 
     const size_t lds = a.tab_lds + (size_t)BB_WAVES_PER_BLOCK * (a.in_lds + 4u * a.ok_words);   // 22 .. 46 KiB
     const dim3 grid = tables_grid(a.nwork, lds);
     hipLaunchKernelGGL(k_recode_tables, grid, dim3(BB_BLOCK), lds, (hipStream_t)stream, a);
+    BB_HIP(hipGetLastError());
+    return BB_OK;
+}
+
+// ---- power and moments per component and time bin from int8 block streams (k_moments.h).
+//      EXTENSION: no reference counterpart. ----
+// What the parameters alone decide, and with it the access shape and the output map of the kernel's arguments.
+static int moments_params_check(const bb_moments_params *p, bb_moments_args *a)
+{
+    if (!p) return BB_EINVAL;
+    if (p->layout == BB_MOMENTS_MKBF) return BB_ENOTSUP;                      // heaps of 256 times: not taken
+    if (p->layout != BB_MOMENTS_GUPPI_CF && p->layout != BB_MOMENTS_GUPPI_TF && p->layout != BB_MOMENTS_ROWS) return BB_EINVAL;
+    if (p->npol < 1 || p->nchan < 1 || (p->ncomp != 1 && p->ncomp != 2) || p->ntime < 1) return BB_EINVAL;
+    if (p->t_lo > p->t_hi || p->t_hi > p->ntime || p->bin_rows == 0 || p->src0 < 0 || p->src_stride < 0) return BB_EINVAL;
+    if (p->npol > (1 << 20) || p->nchan > (1 << 20) || p->ntime > (1ull << 40)) return BB_ENOTSUP;
+    const uint64_t R = (uint64_t)p->npol * (uint64_t)p->nchan * (uint64_t)p->ncomp;   // components of a time
+    if (R > BB_MOMENTS_MAX_ROW) return BB_ENOTSUP;
+    a->bin_elems = (uint32_t)R;
+    a->pay_bytes = p->ntime * R;
+    a->pitch = 0; a->nrun = 1; a->c_stride = 0; a->tf = 0; a->nchan = (uint32_t)p->nchan;
+    a->P = 0; a->Rb = 0;
+    if (p->layout == BB_MOMENTS_ROWS) {
+        if (R == 1 || R == 2 || R == 4) a->P = (uint32_t)R;                   // one run; component = byte phase
+        else if (R % 4 == 0) a->Rb = (uint32_t)R;
+        else return BB_ENOTSUP;
+        for (uint32_t j = 0; j < 4; ++j) a->ph_off[j] = a->P ? j % a->P : 0;
+    } else {
+        if (p->ncomp != 2 || p->npol > 2 || (p->layout == BB_MOMENTS_GUPPI_TF && p->npol != 2)) return BB_ENOTSUP;
+        const uint32_t P = (uint32_t)p->npol * 2;                             // bytes per time of a channel
+        if (p->layout == BB_MOMENTS_GUPPI_TF && p->nchan > 1) {
+            a->Rb = (uint32_t)R; a->tf = 1;
+        } else {                                                              // (time first with one channel is a run as well)
+            a->P = P;
+            if (p->layout == BB_MOMENTS_GUPPI_CF) { a->nrun = (uint32_t)p->nchan; a->pitch = p->ntime * P; a->c_stride = 2; }
+        }
+        for (uint32_t j = 0; j < 4; ++j) a->ph_off[j] = ((j % P) / 2) * (uint32_t)p->nchan * 2 + (j & 1);
+    }
+    if (((uint64_t)p->src0 | (uint64_t)p->src_stride | a->pitch) & 3) return BB_ENOTSUP;   // payloads and runs begin on dwords
+    return BB_OK;
+}
+
+int bb_i8_moments_check(const bb_moments_params *p) { bb_moments_args a; return moments_params_check(p, &a); }
+
+#define BB_MOMENTS_GRID 1024ull                      // workgroups: what 256 CUs hold at once at 4 waves per SIMD; every wave flushes at its end, and 2048 took twice as long on one bin
+
+int bb_i8_moments(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size_t nframes,
+                  const bb_moments_params *p, int64_t *d_sums, size_t sums_elems, void *stream)
+{
+    bb_moments_args a;
+    int rc = moments_params_check(p, &a);
+    if (rc) return rc;
+    if (!d_sums || ((uintptr_t)d_sums & 7)) return BB_EINVAL;
+    if (p->nbins > (~0ull) / (2 * (uint64_t)a.bin_elems) || sums_elems < p->nbins * 2 * (uint64_t)a.bin_elems) return BB_ERANGE;
+    if (p->first_row > (1ull << 56)) return BB_ERANGE;
+    a.nt = p->t_hi - p->t_lo;
+    if (nframes && a.nt > (1ull << 56) / (uint64_t)nframes) return BB_ERANGE;
+    const uint64_t nrows = (uint64_t)nframes * a.nt;                          // rows of the series that this call adds
+    if (!nrows) return BB_OK;
+    if ((p->first_row + (nrows - 1)) / p->bin_rows >= p->nbins) return BB_ERANGE;   // the last row's bin
+    if (!d_buf) return BB_EINVAL;
+    if ((uintptr_t)d_buf & 3) return BB_ENOTSUP;
+    if (!d_src && (uint64_t)p->src_stride > (1ull << 62) / (uint64_t)nframes) return BB_ERANGE;
+    rc = packed_source(a, d_buf, buf_nbytes, d_src, p->src0, p->src_stride, (uint64_t)nframes, a.pay_bytes);
+    if (rc) return rc;
+    a.sums = (long long *)d_sums;
+    a.nframes = nframes;
+    a.t_lo = p->t_lo;
+    a.first_row = p->first_row; a.bin_rows = p->bin_rows; a.nbins = p->nbins;
+    uint64_t units;                                                           // runs or column blocks
+    if (a.P) {
+        a.mode = BB_MOM_RUN;
+        const uint64_t nst = (a.nt * a.P + 15 + BB_MOM_STEP - 1) / BB_MOM_STEP;   // wave loads of a run, at most
+        a.nseg = (nst + BB_MOM_RUN_STEPS - 1) / BB_MOM_RUN_STEPS;
+        a.NV = a.rpl = a.chunk_rows = 0;
+        units = a.nrun;
+    } else {
+        // 16 bytes per lane where every row of every payload begins on 16 bytes, else dwords
+        const bool v4 = !d_src && a.Rb % 16 == 0 && !((uintptr_t)d_buf & 15) && !(((uint64_t)p->src0 | (uint64_t)p->src_stride) & 15);
+        a.mode = v4 ? BB_MOM_ROW4 : BB_MOM_ROW1;
+        a.NV = a.Rb / (v4 ? 16u : 4u);
+        a.rpl = a.NV < BB_WAVE ? BB_WAVE / a.NV : 1u;
+        a.chunk_rows = a.rpl * BB_MOM_ROW_STEPS;
+        a.nseg = (a.nt + a.chunk_rows - 1) / a.chunk_rows;
+        a.nrun = (a.NV + BB_WAVE - 1) / BB_WAVE;
+        units = a.nrun;
+    }
+    if (a.nseg > (~0ull) / (uint64_t)nframes || a.nseg * (uint64_t)nframes > (~0ull) / units) return BB_ERANGE;
+    a.nwork = a.nseg * (uint64_t)nframes * units;
+    // one contiguous range of items per wave, as many waves as the device holds at once
+    const uint64_t waves = std::min<uint64_t>(a.nwork, BB_MOMENTS_GRID * BB_WAVES_PER_BLOCK);
+    a.per = (a.nwork + waves - 1) / waves;
+    const uint64_t ranges = (a.nwork + a.per - 1) / a.per;
+    const uint64_t g = (ranges + BB_WAVES_PER_BLOCK - 1) / BB_WAVES_PER_BLOCK;
+    hipLaunchKernelGGL(k_i8_moments, dim3((unsigned)g), dim3(BB_BLOCK), 0, (hipStream_t)stream, a);
+    BB_NOTE("k_i8_moments<%s> grid %u items %llu", a.mode == BB_MOM_RUN ? "run" : a.mode == BB_MOM_ROW4 ? "rows16" : "rows4",
+            (unsigned)g, (unsigned long long)a.nwork);
     BB_HIP(hipGetLastError());
     return BB_OK;
 }

@@ -18,6 +18,7 @@
 #include "k_requant.h"
 #include "k_recode.h"
 #include "k_recode_tables.h"
+#include "k_moments.h"
 #include "k_tfpick.h"
 #if BB_EXP
 #include "k_burst.h"
@@ -1687,11 +1688,7 @@ static int mark4_scan_impl(const void *d_buf, size_t nbytes, const bb_mark4_scan
     const dim3 block(BB_BLOCK);
     hipStream_t st = (hipStream_t)stream;
     const uint8_t *b = (const uint8_t *)d_buf;
-    switch (p->ntrack) {
-        case 16: hipLaunchKernelGGL(k_mark4_scan<16>, grid, block, 0, st, b, (uint64_t)nbytes, *p, d_offsets, d_recs, (uint64_t)nframes); break;
-        case 32: hipLaunchKernelGGL(k_mark4_scan<32>, grid, block, 0, st, b, (uint64_t)nbytes, *p, d_offsets, d_recs, (uint64_t)nframes); break;
-        default: hipLaunchKernelGGL(k_mark4_scan<64>, grid, block, 0, st, b, (uint64_t)nbytes, *p, d_offsets, d_recs, (uint64_t)nframes); break;
-    }
+    hipLaunchKernelGGL(k_mark4_scan, grid, block, 0, st, b, (uint64_t)nbytes, *p, d_offsets, d_recs, (uint64_t)nframes);
     BB_HIP(hipGetLastError());
     return BB_OK;
 }

@@ -96,25 +96,36 @@ void k_mark4_locate(const uint8_t *buf, uint64_t nbytes, int64_t *out, uint64_t 
         });
 }
 
-template <int NTRACK>
+// One kernel for the three track counts (two word loads per lane): p.ntrack picks the
+// word type in a wave-uniform switch, the word travels zero-extended in 64 bits.
+__device__ __forceinline__ uint64_t bb_m4_load_ntrack(const uint8_t *buf, uint64_t pos, uint32_t ntrack)
+{
+    switch (ntrack) {
+    case 16: return bb_m4_load_any<16>(buf, pos);
+    case 32: return bb_m4_load_any<32>(buf, pos);
+    default: return bb_m4_load_any<64>(buf, pos);
+    }
+}
+
 __global__ __launch_bounds__(BB_BLOCK)
 void k_mark4_scan(const uint8_t *buf, uint64_t nbytes, bb_mark4_scan_params p,
                   const int64_t *offsets, bb_frame_rec *recs, uint64_t nframes)
 {
-    typedef typename bb_m4_word<NTRACK>::type word_t;
     const uint64_t frame = (uint64_t)blockIdx.x * BB_WAVES_PER_BLOCK + bb_wave();
     if (frame >= nframes) return;                       // wave-uniform
     const int lane = bb_lane();
-    const uint64_t frame_nbytes = (uint64_t)NTRACK * 2500;
+    const uint32_t ntrack = (uint32_t)p.ntrack;         // 16, 32 or 64 (the host checks)
+    const uint64_t wsz = ntrack / 8;                    // bytes of a stream word
+    const uint64_t frame_nbytes = (uint64_t)ntrack * 2500;
     // fixed stride, or explicit (possibly odd) offsets from bb_mark4_locate
     const uint64_t off = offsets ? (uint64_t)offsets[frame] : p.first_offset + frame * frame_nbytes;
     const bool whole = off + frame_nbytes <= nbytes;
-    word_t a = 0, b = 0;
+    uint64_t a = 0, b = 0;
     if (whole) {
-        a = bb_m4_load_any<NTRACK>(buf, off + (uint64_t)(32 + lane) * sizeof(word_t));
-        b = bb_m4_load_any<NTRACK>(buf, off + (uint64_t)(96 + lane) * sizeof(word_t));
+        a = bb_m4_load_ntrack(buf, off + (uint64_t)(32 + lane) * wsz, ntrack);
+        b = bb_m4_load_ntrack(buf, off + (uint64_t)(96 + lane) * wsz, ntrack);
     }
-    const word_t ones = (word_t)~(word_t)0;
+    const uint64_t ones = ~0ull >> (64 - ntrack);
     // error flags: header word 1 bits 15..12 -> stream words 48..51
     const bool err = lane >= 16 && lane < 20 && a != 0;
     // sync: stream word 63 all zero, words 64..95 all ones

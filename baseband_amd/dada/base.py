@@ -184,6 +184,15 @@ class DADAStreamReader(BlockStreamReader):
             self._flat_rows(dbuf, 1, 0, (b - a) * rb, 0, out_flat)
         return pieces, decode
 
+    def _moments_geometry(self):
+        if self._mkbf:
+            return "MKBF heaps have no moments kernel"
+        return _lib.MOMENTS_ROWS, 2 if self.complex_data else 1
+
+    def _moments_ntime(self, frame):
+        # (a last frame that is cut short holds `_last_rows` samples)
+        return self._last_rows if frame == self._nframes - 1 else self._spf0
+
     def _half_geometry(self):
         # plain int8 samples go through bb_decode_frames, `n` bytes per frame (any multiple of 4)
         return (_lib.CODER_INT, 8, 1, 1, 4) if self.bps == 8 and not self._mkbf else None

@@ -149,6 +149,14 @@ class GUPPIStreamReader(BlockStreamReader):
                                     src0=skip, out=out_flat, nchan_stored=stored)
         return pieces, decode
 
+    def _moments_geometry(self):
+        if not self.complex_data:
+            return "real GUPPI samples have no moments kernel"
+        return (_lib.MOMENTS_GUPPI_CF if self.header0.channels_first else _lib.MOMENTS_GUPPI_TF), 2
+
+    def _moments_ntime(self, frame):
+        return self._spf_full                   # (the overlap is stored in every block)
+
     def _decode_window(self, dbuf, nframes, a, b, out_flat, payload_offset,
                        frame_stride, first_frame):
         h = self.header0

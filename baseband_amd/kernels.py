@@ -646,6 +646,40 @@ def count_states_bins(dbuf, nframes, payload_nbytes, bps, chunk, nslot, bin_rows
     return counts
 
 
+def _fits(*values):
+    """Are these all integers that the parameter block's fields hold?"""
+    return all(0 <= v < 1 << 31 for v in values[:4]) and all(0 <= v < 1 << 63 for v in values[4:])
+
+
+def i8_moments_supported(layout, npol, nchan, ncomp, ntime, t_lo=0, t_hi=None, bin_rows=1, src0=0, src_stride=0):
+    """Would `i8_moments` take this geometry?  (bb_i8_moments_check; no device needed.)"""
+    if t_hi is None:
+        t_hi = ntime
+    if not _fits(layout, npol, nchan, ncomp, ntime, t_lo, t_hi, bin_rows, src0, src_stride):
+        return False
+    return _lib.i8_moments_check(layout, npol, nchan, ncomp, ntime, t_lo, t_hi, bin_rows, src0, src_stride) == _lib.BB_OK
+
+
+def i8_moments(dbuf, nframes, layout, npol, nchan, ncomp, ntime, t_lo, t_hi, bin_rows, nbins, first_row=0,
+               src0=0, src_stride=0, src=None, sums=None):
+    """Sums of x and of x * x per component and time bin from stored int8 samples (bb_i8_moments;
+    EXTENSION, no reference counterpart): times [t_lo, t_hi) of `nframes` payloads of `ntime`
+    times each, in `layout` (``_lib.MOMENTS_GUPPI_CF``, ``_GUPPI_TF``, ``_ROWS``), taken through
+    the index `src` (-1 or an offset outside the buffer: adds nothing) or at ``src0 + k *
+    src_stride``.  Time t of frame f is row ``first_row + f * (t_hi - t_lo) + (t - t_lo)`` of a
+    series and lands in bin ``row // bin_rows`` -> int64 device tensor of shape ``(nbins, npol,
+    nchan, ncomp, 2)``, the last axis (sum of x, sum of x * x).  With `sums` (such a tensor,
+    contiguous) the call ADDS to it: windows of a file and pieces with different row ranges fill
+    one answer.  Nothing is decoded and nothing synchronises."""
+    p = _lib.moments_params(layout, npol, nchan, ncomp, ntime, t_lo, t_hi, bin_rows, nbins, first_row, src0, src_stride)
+    if not _given(sums, 'sums', torch.int64):
+        check(lib.bb_i8_moments_check(C.byref(p)), 'bb_i8_moments')          # (before a shape is made of the parameters)
+        sums = torch.zeros((nbins, npol, nchan, ncomp, 2), dtype=torch.int64, device=dbuf.device)
+    check(lib.bb_i8_moments(_ptr(dbuf), dbuf.numel(), _ptr(src), nframes, C.byref(p), _ptr(sums), sums.numel(),
+                            _stream(dbuf)), 'bb_i8_moments')
+    return sums
+
+
 REPACK_MAX_ROW_BITS = 256      # nslot * chunk * bps the repack kernel takes
 REPACK_MAX_SLOTS = 32          # ... and thread slots on either side
 

@@ -713,6 +713,83 @@ int bb_count_states_bins(const void *d_buf, size_t buf_nbytes,
                          uint32_t *d_counts, size_t ncounts, void *stream);
 int bb_count_states_bins_check(const bb_states_params *params, uint64_t bin_rows);
 
+/* ---- power and moments from int8 block streams (EXTENSION) ---------------- */
+
+/*
+ * The sums of x and of x * x of every real component of every sample, per time
+ * bin, from the stored int8 bytes of GUPPI raw blocks and plain DADA frames:
+ * one read of the payloads, nothing is decoded.  The reference has no
+ * counterpart (there: a read, then a reduction over the float32 samples).
+ *
+ * Time t in [t_lo, t_hi) of frame f of the call is row
+ *     first_row + f * (t_hi - t_lo) + (t - t_lo)
+ * of a series and lands in bin row / bin_rows.  Component k (0: real, 1:
+ * imaginary; ncomp = 1: real data) of polarisation p and channel c of that
+ * time ADDS x to
+ *     d_sums[(((bin * npol + p) * nchan + c) * ncomp + k) * 2]
+ * and x * x to the element behind it (int64; the reader's sample order).  The
+ * caller zeroes d_sums: windows of a file and pieces with different row ranges
+ * fill one answer by several calls with continuing first_row.  Integer adds
+ * commute: the result is the same bit for bit from run to run.
+ *
+ * Layouts (an enum of their own; enum bb_layout is not touched):
+ *   BB_MOMENTS_GUPPI_CF  (chan, time, pol, re/im), npol 1 or 2, ncomp 2
+ *   BB_MOMENTS_GUPPI_TF  (time, chan, pol, re/im), npol 2, ncomp 2
+ *   BB_MOMENTS_ROWS      (time, pol, chan, comp) as plain DADA stores them, with
+ *                        R = npol * nchan * ncomp in {1, 2, 4} or a multiple of 4
+ *   BB_MOMENTS_MKBF      MeerKAT beamformer heaps: NOT taken (BB_ENOTSUP); decode
+ *                        and reduce instead
+ *
+ * Frames as for bb_decode_frames: through the index d_src (offsets that are
+ * multiples of 4; -1, any negative one, one whose payload of ntime times does
+ * not lie wholly inside the buffer or one off a dword adds nothing) or at
+ * src0 + f * src_stride.  Nothing outside times [t_lo, t_hi) of a payload is
+ * read, but for the rest of a dword that holds an edge.
+ *
+ * bb_i8_moments_check answers what the parameters alone decide (no buffers, no
+ * device), in this order: BB_EINVAL for a NULL block; BB_ENOTSUP for
+ * BB_MOMENTS_MKBF, BB_EINVAL for an unknown layout; BB_EINVAL for npol, nchan
+ * or ntime < 1, ncomp not 1 or 2, t_lo > t_hi, t_hi > ntime, bin_rows == 0, a
+ * negative src0 or src_stride; BB_ENOTSUP for a geometry the kernel does not
+ * take (npol > 2 or real data in a GUPPI layout, npol 1 time first, R not as
+ * above, R > 2^22, more than 2^20 channels or polarisations, ntime > 2^40);
+ * BB_ENOTSUP when src0, src_stride or the channel pitch ntime * npol * 2 of
+ * BB_MOMENTS_GUPPI_CF is not a multiple of 4.
+ *
+ * The call answers in addition BB_EINVAL when d_sums is NULL or not 8-byte
+ * aligned, BB_ERANGE when sums_elems < nbins * npol * nchan * ncomp * 2, when
+ * first_row or nframes * (t_hi - t_lo) exceeds 2^56 or when the last row's bin
+ * is >= nbins, BB_EINVAL for a NULL d_buf, BB_ENOTSUP for one that is not
+ * 4-byte aligned, BB_ERANGE when a fixed-stride payload ends outside the
+ * buffer.  Stream-ordered, never allocates, never synchronises; nframes == 0 or
+ * t_lo == t_hi launches nothing; an argument error leaves d_sums untouched.
+ */
+enum bb_moments_layout {
+    BB_MOMENTS_GUPPI_CF = 0,
+    BB_MOMENTS_GUPPI_TF = 1,
+    BB_MOMENTS_ROWS     = 2,
+    BB_MOMENTS_MKBF     = 3
+};
+#define BB_MOMENTS_MAX_ROW (1u << 22)   /* npol * nchan * ncomp at most */
+
+typedef struct bb_moments_params {
+    int32_t  layout;          /* enum bb_moments_layout */
+    int32_t  npol, nchan;
+    int32_t  ncomp;           /* 2: complex, 1: real */
+    uint64_t ntime;           /* times stored in a payload */
+    uint64_t t_lo, t_hi;      /* times [t_lo, t_hi) of every payload are added */
+    int64_t  src0, src_stride;/* used when d_src == NULL */
+    uint64_t bin_rows;        /* rows of the series per bin */
+    uint64_t first_row;       /* place of the call's first row in the series */
+    uint64_t nbins;           /* bins of d_sums */
+} bb_moments_params;
+
+int bb_i8_moments(const void *d_buf, size_t buf_nbytes,
+                  const int64_t *d_src, size_t nframes,
+                  const bb_moments_params *params,
+                  int64_t *d_sums, size_t sums_elems, void *stream);
+int bb_i8_moments_check(const bb_moments_params *params);
+
 /* ---- format conversion on the packed bytes -------------------------------- */
 
 /*
