@@ -8,46 +8,14 @@ import pytest
 
 import guardkit
 import seamkit as sk
+from momentkit import CF, TF, ROWS, oracle, row_bytes, samples
 
 pytestmark = pytest.mark.gpu
-
-CF, TF, ROWS = 0, 1, 2
 
 
 def _torch():
     import torch
     return torch
-
-
-def row_bytes(layout, npol, nchan, ncomp):
-    return npol * nchan * ncomp
-
-
-def samples(payload, layout, npol, nchan, ncomp, ntime):
-    """int64 (time, pol, chan, comp) of one stored payload."""
-    x = payload.view(np.int8).astype(np.int64)
-    if layout == CF:
-        return x.reshape(nchan, ntime, npol, 2).transpose(1, 2, 0, 3)
-    if layout == TF:
-        return x.reshape(ntime, nchan, npol, 2).transpose(0, 2, 1, 3)
-    return x.reshape(ntime, npol, nchan, ncomp)
-
-
-def oracle(buf, offsets, layout, npol, nchan, ncomp, ntime, t_lo, t_hi, bin_rows, nbins, first_row=0, sums=None):
-    """What bb_i8_moments adds for the frames at `offsets` of the NumPy byte buffer `buf`."""
-    if sums is None:
-        sums = np.zeros((nbins, npol, nchan, ncomp, 2), np.int64)
-    pay, nt = ntime * row_bytes(layout, npol, nchan, ncomp), t_hi - t_lo
-    for f, so in enumerate(offsets):
-        so = int(so)
-        if so < 0 or so + pay > buf.size or so % 4 or nt == 0:
-            continue
-        x = samples(buf[so:so + pay], layout, npol, nchan, ncomp, ntime)[t_lo:t_hi]
-        bins = (first_row + f * nt + np.arange(nt)) // bin_rows
-        starts = np.r_[0, np.flatnonzero(np.diff(bins)) + 1]
-        sums[bins[starts], ..., 0] += np.add.reduceat(x, starts, axis=0)
-        sums[bins[starts], ..., 1] += np.add.reduceat(x * x, starts, axis=0)
-    return sums
 
 
 def launch(dbuf, nframes, geom, ntime, t_lo, t_hi, bin_rows, nbins, **kw):
