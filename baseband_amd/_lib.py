@@ -258,6 +258,8 @@ SIGNATURES = [
     ('bb_count_states_bins_check', C.c_int, [C.POINTER(StatesParams), C.c_uint64]),
     ('bb_i8_moments', C.c_int, [_vp, _sz, _vp, _sz, C.POINTER(MomentsParams), _vp, _sz, _vp]),
     ('bb_i8_moments_check', C.c_int, [C.POINTER(MomentsParams)]),
+    ('bb_i8_coherence', C.c_int, [_vp, _sz, _vp, _sz, C.POINTER(MomentsParams), _vp, _sz, _vp]),
+    ('bb_i8_coherence_check', C.c_int, [C.POINTER(MomentsParams)]),
     ('bb_repack_frames', C.c_int, [_vp, _sz, _vp, _sz, C.POINTER(RepackParams), _vp, _sz, _vp]),
     ('bb_repack_check', C.c_int, [C.POINTER(RepackParams)]),
     ('bb_requant_frames', C.c_int, [_vp, _sz, _vp, _sz, C.POINTER(RequantParams), _vp, _sz, _vp]),
@@ -372,6 +374,13 @@ def i8_moments_check(layout, npol, nchan, ncomp, ntime, t_lo=0, t_hi=0, bin_rows
     (bb_i8_moments_check: no buffers, no device): BB_OK, BB_EINVAL or BB_ENOTSUP."""
     p = moments_params(layout, npol, nchan, ncomp, ntime, t_lo, t_hi, bin_rows, 0, 0, src0, src_stride)
     return lib.bb_i8_moments_check(C.byref(p))
+
+
+def i8_coherence_check(layout, npol, nchan, ncomp, ntime, t_lo=0, t_hi=0, bin_rows=1, src0=0, src_stride=0):
+    """What `bb_i8_coherence` would answer to these parameters, as far as they decide it
+    (bb_i8_coherence_check: no buffers, no device): BB_OK, BB_EINVAL or BB_ENOTSUP."""
+    p = moments_params(layout, npol, nchan, ncomp, ntime, t_lo, t_hi, bin_rows, 0, 0, src0, src_stride)
+    return lib.bb_i8_coherence_check(C.byref(p))
 
 
 def repack_params(bps, coder_in, coder_out, chunk_in, nslot_in, chunk_out, nslot_out, payload_in, payload_out,

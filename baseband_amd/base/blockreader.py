@@ -352,6 +352,52 @@ class BlockStreamReader(GPUStreamReaderBase):
                                                                self._frame_nbytes))
         return layout, npol, nchan, ncomp
 
+    def _launch_per_run(self, count, add):
+        """The walk of `moment_series` and `coherence_series` over the samples ``read(count)`` would
+        return from the offset: ``add(dbuf, nframes, a, b, nt, first_row)`` once per run of frames that
+        share a row range [a, b) and a payload of `nt` times -- from the resident bytes, from the
+        frame that small reads keep staged, or window by window -- with `first_row` the place of
+        the run's (the window's) first sample in the request."""
+        # runs of frames that share a row range and a payload size: one launch each (per window)
+        runs = []
+        for f, a, b in self._pieces(self.offset, count):
+            nt = self._moments_ntime(f)
+            if runs and runs[-1][1] == f and tuple(runs[-1][2:]) == (a, b, nt):
+                runs[-1][1] = f + 1
+            else:
+                runs.append([f, f + 1, a, b, nt])
+        image = self._image()
+        resident = self._resident_bytes()
+        done = 0
+        for f0, f1, a, b, nt in runs:
+            if resident is not None:
+                lo = self._frame_span(f0)[0]
+                last_lo, last_n = self._frame_span(f1 - 1)
+                add(self._device_window(resident, lo, min(last_lo + last_n, resident.numel())), f1 - f0, a, b, nt, done)
+            elif f1 == f0 + 1 and self._ahead is not None and self._ahead[0] == f0:
+                add(self._ahead[1], 1, a, b, nt, done)      # the frame that small reads keep staged
+            else:
+                nbytes = self._frame_span(f0)[1]
+                per_win = max(1, self.window_bytes // self._frame_nbytes)
+                cap = max(per_win * self._frame_nbytes, nbytes)
+                if self._pipeline is None or self._pipeline.cap < cap:
+                    self._pipeline = WindowPipeline(image, cap)
+                ranges, spans = [], []
+                for s in range(f0, f1, per_win):
+                    e = min(f1, s + per_win)
+                    lo = self._frame_span(s)[0]
+                    last_lo, last_n = self._frame_span(e - 1)
+                    ranges.append((lo, min(last_lo + last_n, len(image))))
+                    spans.append((s, e))
+
+                def process(dbuf, i, base=done, a=a, b=b, nt=nt, f0=f0):
+                    s, e = spans[i]
+                    add(dbuf, e - s, a, b, nt, base + (s - f0) * (b - a))
+
+                self._pipeline.run(ranges, process)
+            done += (f1 - f0) * (b - a)
+        assert done == count
+
     def moment_series(self, bin_samples, count=None, packed=None):
         """Sum of x and sum of x * x of every real component per time bin, over the samples
         ``read(count)`` would return from the current offset -> int64 device tensor of shape
@@ -390,50 +436,12 @@ class BlockStreamReader(GPUStreamReaderBase):
             return self._moments_by_read(bin_samples, count, nbins)
         layout, npol, nchan, ncomp = plan
         sums = torch.zeros((nbins, npol, nchan, ncomp, 2), dtype=torch.int64, device='cuda')
-        # runs of frames that share a row range and a payload size: one launch each (per window)
-        runs = []
-        for f, a, b in self._pieces(self.offset, count):
-            nt = self._moments_ntime(f)
-            if runs and runs[-1][1] == f and tuple(runs[-1][2:]) == (a, b, nt):
-                runs[-1][1] = f + 1
-            else:
-                runs.append([f, f + 1, a, b, nt])
-        image = self._image()
-        resident = self._resident_bytes()
-        done = 0
 
         def add(dbuf, nframes, a, b, nt, first_row):
             kernels.i8_moments(dbuf, nframes, layout, npol, nchan, ncomp, nt, a, b, bin_samples, nbins,
                                first_row=first_row, src0=self._header_nbytes, src_stride=self._frame_nbytes, sums=sums)
 
-        for f0, f1, a, b, nt in runs:
-            if resident is not None:
-                lo = self._frame_span(f0)[0]
-                last_lo, last_n = self._frame_span(f1 - 1)
-                add(self._device_window(resident, lo, min(last_lo + last_n, resident.numel())), f1 - f0, a, b, nt, done)
-            elif f1 == f0 + 1 and self._ahead is not None and self._ahead[0] == f0:
-                add(self._ahead[1], 1, a, b, nt, done)      # the frame that small reads keep staged
-            else:
-                nbytes = self._frame_span(f0)[1]
-                per_win = max(1, self.window_bytes // self._frame_nbytes)
-                cap = max(per_win * self._frame_nbytes, nbytes)
-                if self._pipeline is None or self._pipeline.cap < cap:
-                    self._pipeline = WindowPipeline(image, cap)
-                ranges, spans = [], []
-                for s in range(f0, f1, per_win):
-                    e = min(f1, s + per_win)
-                    lo = self._frame_span(s)[0]
-                    last_lo, last_n = self._frame_span(e - 1)
-                    ranges.append((lo, min(last_lo + last_n, len(image))))
-                    spans.append((s, e))
-
-                def process(dbuf, i, base=done, a=a, b=b, nt=nt, f0=f0):
-                    s, e = spans[i]
-                    add(dbuf, e - s, a, b, nt, base + (s - f0) * (b - a))
-
-                self._pipeline.run(ranges, process)
-            done += (f1 - f0) * (b - a)
-        assert done == count
+        self._launch_per_run(count, add)
         if ncomp == 1:
             sums = sums.reshape(nbins, npol, nchan, 2)
         # squeeze and subset, as read() applies them to a sample
@@ -448,6 +456,17 @@ class BlockStreamReader(GPUStreamReaderBase):
         decoded samples, summed in int64 (exact: the decoded values are the stored integers)."""
         comp = (2,) if self.complex_data else ()
         sums = torch.zeros((nbins,) + tuple(self.sample_shape) + comp + (2,), dtype=torch.int64, device='cuda')
+
+        def values(data):
+            x = (torch.view_as_real(data) if self.complex_data else data).to(torch.int64)
+            return torch.stack((x, x * x), -1)
+
+        return self._binned_by_read(bin_samples, count, sums, values)
+
+    def _binned_by_read(self, bin_samples, count, sums, values):
+        """``values(data)`` (int64, a row per sample) of ``read()`` in pieces of at most
+        `moments_fallback_bytes` of decoded samples, added up per bin into `sums`; the offset
+        does not move."""
         per_sample = 4 * max(1, int(np.prod(self.sample_shape))) * (2 if self.complex_data else 1)
         step = max(1, self.moments_fallback_bytes // per_sample)
         offset, host = self.offset, self.host_results
@@ -455,10 +474,7 @@ class BlockStreamReader(GPUStreamReaderBase):
         try:
             for lo in range(0, count, step):
                 n = min(step, count - lo)
-                data = self.read(n)
-                x = (torch.view_as_real(data) if self.complex_data else data).to(torch.int64)
-                del data
-                x = torch.stack((x, x * x), -1)
+                x = values(self.read(n))
                 # the rows up to the next bin edge, whole bins, the rest
                 head = min(n, -lo % bin_samples)
                 whole = (n - head) // bin_samples
@@ -490,3 +506,119 @@ class BlockStreamReader(GPUStreamReaderBase):
         if nbins:
             n[-1] = count - (nbins - 1) * operator.index(bin_samples)
         return sq.double() / n.double().reshape((nbins,) + (1,) * (sq.dim() - 1))
+
+    # -- cross-polarisation products per channel and time bin from the stored int8 bytes (kernels.i8_coherence)
+    def _coherence_channels(self):
+        """The channels of the answer: squeeze and subset applied to the index grid of (npol, nchan)
+        must leave polarisation 0, then polarisation 1, over the same channels -> int64 array of
+        those channels, shaped as the channel part of a sample."""
+        npol, nchan = self._unsliced_shape
+        if npol != 2:
+            raise ValueError("coherence_series needs a stream of exactly two polarisations, not {}".format(npol))
+        grid = np.arange(npol * nchan).reshape(npol, nchan)
+        if self.squeeze:
+            grid = grid.reshape(_apply_squeeze(grid.shape))
+        if self.subset:
+            grid = grid[tuple(np.asarray(s) if isinstance(s, list) else s for s in self.subset)]
+        grid = np.asarray(grid)
+        if grid.ndim < 1 or grid.shape[0] != 2 or (grid[0] >= nchan).any() or not np.array_equal(grid[1], grid[0] + nchan):
+            raise ValueError("coherence_series: the subset must keep both polarisations, 0 then 1, over the same "
+                             "channels; this one selects (pol, chan) = {}".format(
+                                 [divmod(int(i), nchan) for i in grid.reshape(-1)[:8]]))
+        return grid[0]
+
+    def _coherence_plan(self, bin_samples):
+        """``(layout, nchan)`` where the kernel takes this stream with bins of `bin_samples`, else
+        the reason as a str."""
+        geom = self._moments_geometry()
+        if isinstance(geom, str):
+            return geom
+        layout, ncomp = geom
+        if ncomp != 2:
+            return "real samples have no coherence kernel"
+        nchan = self._unsliced_shape[1]
+        for ntime in {self._moments_ntime(0), self._moments_ntime(self._nframes - 1)}:
+            if not kernels.i8_coherence_supported(layout, nchan, ntime, bin_rows=bin_samples,
+                                                  src0=self._header_nbytes, src_stride=self._frame_nbytes):
+                return ("the coherence kernel does not take 2 pol x {} chan, {} times a frame, payloads at "
+                        "{} + k * {} bytes".format(nchan, ntime, self._header_nbytes, self._frame_nbytes))
+        return layout, nchan
+
+    def coherence_series(self, bin_samples, count=None, packed=None):
+        """Cross-polarisation products per channel and time bin of a stream of two polarisations
+        X, Y, over the samples ``read(count)`` would return from the current offset -> int64
+        device tensor of shape ``(nbins, nchan, 4)`` (``(nbins, 4)`` with `squeeze` and one
+        channel), ``nbins = ceil(count / bin_samples)``; the last axis is (sum ``|X|**2``, sum
+        ``|Y|**2``, Re sum ``X * conj(Y)``, Im sum ``X * conj(Y)``).  Bins as in `moment_series`;
+        the offset does not move.  A `subset` must keep both polarisations over the same
+        channels (`ValueError` otherwise); those channels select from the answer.
+
+        With ``packed=None`` the sums come from the stored int8 bytes where the kernel takes the
+        stream (bb_i8_coherence: one pass over the file's bytes, nothing is decoded) and from
+        ``read()`` in pieces followed by a reduction elsewhere (MKBF heaps, an odd number of
+        channels above one in plain DADA, payloads off a dword, real samples: X * Y, then 0);
+        both are exact.  ``packed=False`` always reads and reduces, ``packed=True`` raises
+        `NotImplementedError` where the kernel does not take the stream."""
+        if self.closed:
+            raise ValueError("I/O operation on closed stream.")
+        bin_samples = operator.index(bin_samples)
+        if bin_samples < 1:
+            raise ValueError("coherence_series: bin_samples must be at least 1")
+        if self.bps != 8:
+            raise NotImplementedError("coherence_series: samples of {} bits are not int8".format(self.bps))
+        chans = self._coherence_channels()
+        left = self.shape[0] - self.offset
+        if count is None or count < 0:
+            count = max(0, left)
+        if count > left:
+            raise EOFError("cannot read from beyond end of input.")
+        kernels.require_gpu()
+        nbins = -(-count // bin_samples)
+        plan = None if packed is False else self._coherence_plan(bin_samples)
+        if isinstance(plan, str):
+            if packed:
+                raise NotImplementedError("coherence_series: " + plan)
+            plan = None
+        if plan is None:
+            return self._coherence_by_read(bin_samples, count, nbins, chans.shape)
+        layout, nchan = plan
+        sums = torch.zeros((nbins, nchan, 4), dtype=torch.int64, device='cuda')
+
+        def add(dbuf, nframes, a, b, nt, first_row):
+            kernels.i8_coherence(dbuf, nframes, layout, nchan, nt, a, b, bin_samples, nbins,
+                                 first_row=first_row, src0=self._header_nbytes, src_stride=self._frame_nbytes, sums=sums)
+
+        self._launch_per_run(count, add)
+        if not (chans.shape == (nchan,) and np.array_equal(chans, np.arange(nchan))):
+            sums = sums[:, torch.from_numpy(chans.reshape(-1).astype(np.int64)).cuda()]
+        return sums.reshape((nbins,) + chans.shape + (4,))
+
+    def _coherence_by_read(self, bin_samples, count, nbins, chan_shape):
+        """`coherence_series` from ``read()`` in pieces, summed in int64 (exact: the decoded values
+        are the stored integers); a sample is (2,) + `chan_shape` (`_coherence_channels`)."""
+        sums = torch.zeros((nbins,) + tuple(chan_shape) + (4,), dtype=torch.int64, device='cuda')
+
+        def values(data):
+            if not self.complex_data:
+                x, y = data[:, 0].to(torch.int64), data[:, 1].to(torch.int64)
+                return torch.stack((x * x, y * y, x * y, torch.zeros_like(x)), -1)
+            z = torch.view_as_real(data).to(torch.int64)
+            xr, xi, yr, yi = z[:, 0, ..., 0], z[:, 0, ..., 1], z[:, 1, ..., 0], z[:, 1, ..., 1]
+            return torch.stack((xr * xr + xi * xi, yr * yr + yi * yi, xr * yr + xi * yi, xi * yr - xr * yi), -1)
+
+        return self._binned_by_read(bin_samples, count, sums, values)
+
+    def stokes_series(self, bin_samples, count=None, packed=None):
+        """``(XX + YY, XX - YY, 2 Re, 2 Im)`` of `coherence_series` (XX, YY, Re, Im its last axis),
+        divided by the number of samples in the bin (the last bin may be short) -> float64
+        device tensor of the same shape."""
+        c = self.coherence_series(bin_samples, count, packed)
+        nbins = c.shape[0]
+        left = self.shape[0] - self.offset
+        count = max(0, left) if count is None or count < 0 else count
+        n = torch.full((nbins,), operator.index(bin_samples), dtype=torch.int64, device=c.device)
+        if nbins:
+            n[-1] = count - (nbins - 1) * operator.index(bin_samples)
+        xx, yy, re, im = c.unbind(-1)
+        s = torch.stack((xx + yy, xx - yy, 2 * re, 2 * im), -1)
+        return s.double() / n.double().reshape((nbins,) + (1,) * (s.dim() - 1))

@@ -1,5 +1,5 @@
 // The packed-byte entries of bbdecode.hip (bb_count_states, bb_count_states_bins, bb_repack_frames,
-// bb_requant_frames, bb_recode_frames, bb_recode_frames_tables, bb_i8_moments), their argument checks and what they share.  The ORDER of the checks is part of
+// bb_requant_frames, bb_recode_frames, bb_recode_frames_tables, bb_i8_moments, bb_i8_coherence), their argument checks and what they share.  The ORDER of the checks is part of
 // the ABI: tests/golden/abi_return_codes.json holds it in place.
 extern "C++" { namespace {                                   // (the entries have C linkage: the include stands among them)
 // A slot's stream of rows: payloads of whole dwords that hold whole rows of `chunk` codes
@@ -488,57 +488,139 @@ int bb_i8_moments_check(const bb_moments_params *p) { bb_moments_args a; return 
 
 #define BB_MOMENTS_GRID 1024ull                      // workgroups: what 256 CUs hold at once at 4 waves per SIMD; every wave flushes at its end, and 2048 took twice as long on one bin
 
-int bb_i8_moments(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size_t nframes,
-                  const bb_moments_params *p, int64_t *d_sums, size_t sums_elems, void *stream)
+// What bb_i8_moments and bb_i8_coherence check at call time, in this order, after the parameters: the sums
+// (`per_bin` int64 values a bin), the series' rows (*nrows == 0: nothing is asked for), the source
+// -> the members of the kernel's arguments that do not depend on the access shape.
+static int moments_request(bb_moments_args &a, const bb_moments_params *p, const void *d_buf, size_t buf_nbytes,
+                           const int64_t *d_src, size_t nframes, int64_t *d_sums, size_t sums_elems, uint64_t per_bin,
+                           uint64_t *nrows)
 {
-    bb_moments_args a;
-    int rc = moments_params_check(p, &a);
-    if (rc) return rc;
     if (!d_sums || ((uintptr_t)d_sums & 7)) return BB_EINVAL;
-    if (p->nbins > (~0ull) / (2 * (uint64_t)a.bin_elems) || sums_elems < p->nbins * 2 * (uint64_t)a.bin_elems) return BB_ERANGE;
+    if (p->nbins > (~0ull) / per_bin || sums_elems < p->nbins * per_bin) return BB_ERANGE;
     if (p->first_row > (1ull << 56)) return BB_ERANGE;
     a.nt = p->t_hi - p->t_lo;
     if (nframes && a.nt > (1ull << 56) / (uint64_t)nframes) return BB_ERANGE;
-    const uint64_t nrows = (uint64_t)nframes * a.nt;                          // rows of the series that this call adds
-    if (!nrows) return BB_OK;
-    if ((p->first_row + (nrows - 1)) / p->bin_rows >= p->nbins) return BB_ERANGE;   // the last row's bin
+    *nrows = (uint64_t)nframes * a.nt;                                        // rows of the series that this call adds
+    if (!*nrows) return BB_OK;
+    if ((p->first_row + (*nrows - 1)) / p->bin_rows >= p->nbins) return BB_ERANGE;   // the last row's bin
     if (!d_buf) return BB_EINVAL;
     if ((uintptr_t)d_buf & 3) return BB_ENOTSUP;
     if (!d_src && (uint64_t)p->src_stride > (1ull << 62) / (uint64_t)nframes) return BB_ERANGE;
-    rc = packed_source(a, d_buf, buf_nbytes, d_src, p->src0, p->src_stride, (uint64_t)nframes, a.pay_bytes);
+    const int rc = packed_source(a, d_buf, buf_nbytes, d_src, p->src0, p->src_stride, (uint64_t)nframes, a.pay_bytes);
     if (rc) return rc;
     a.sums = (long long *)d_sums;
     a.nframes = nframes;
     a.t_lo = p->t_lo;
     a.first_row = p->first_row; a.bin_rows = p->bin_rows; a.nbins = p->nbins;
-    uint64_t units;                                                           // runs or column blocks
-    if (a.P) {
-        a.mode = BB_MOM_RUN;
-        const uint64_t nst = (a.nt * a.P + 15 + BB_MOM_STEP - 1) / BB_MOM_STEP;   // wave loads of a run, at most
-        a.nseg = (nst + BB_MOM_RUN_STEPS - 1) / BB_MOM_RUN_STEPS;
-        a.NV = a.rpl = a.chunk_rows = 0;
-        units = a.nrun;
-    } else {
-        // 16 bytes per lane where every row of every payload begins on 16 bytes, else dwords
-        const bool v4 = !d_src && a.Rb % 16 == 0 && !((uintptr_t)d_buf & 15) && !(((uint64_t)p->src0 | (uint64_t)p->src_stride) & 15);
-        a.mode = v4 ? BB_MOM_ROW4 : BB_MOM_ROW1;
-        a.NV = a.Rb / (v4 ? 16u : 4u);
-        a.rpl = a.NV < BB_WAVE ? BB_WAVE / a.NV : 1u;
-        a.chunk_rows = a.rpl * BB_MOM_ROW_STEPS;
-        a.nseg = (a.nt + a.chunk_rows - 1) / a.chunk_rows;
-        a.nrun = (a.NV + BB_WAVE - 1) / BB_WAVE;
-        units = a.nrun;
-    }
+    return BB_OK;
+}
+
+// The run form's split: a.nseg items of BB_MOM_RUN_STEPS wave loads per (run, frame).
+static void moments_run_split(bb_moments_args &a)
+{
+    const uint64_t nst = (a.nt * a.P + 15 + BB_MOM_STEP - 1) / BB_MOM_STEP;   // wave loads of a run, at most
+    a.nseg = (nst + BB_MOM_RUN_STEPS - 1) / BB_MOM_RUN_STEPS;
+    a.NV = a.rpl = a.chunk_rows = 0;
+}
+
+// The row forms' split: `nv` lane columns of a row -> rows of a wave load, of an item, items per (column block,
+// frame), column blocks (a.nrun).
+static void moments_rows_split(bb_moments_args &a, uint32_t nv)
+{
+    a.NV = nv;
+    a.rpl = a.NV < BB_WAVE ? BB_WAVE / a.NV : 1u;
+    a.chunk_rows = a.rpl * BB_MOM_ROW_STEPS;
+    a.nseg = (a.nt + a.chunk_rows - 1) / a.chunk_rows;
+    a.nrun = (a.NV + BB_WAVE - 1) / BB_WAVE;
+}
+
+// 16 bytes per lane are possible where every row of every payload begins on 16 bytes
+static bool moments_wide(const bb_moments_params *p, const void *d_buf, const int64_t *d_src)
+{
+    return !d_src && !((uintptr_t)d_buf & 15) && !(((uint64_t)p->src0 | (uint64_t)p->src_stride) & 15);
+}
+
+// a.nseg items per (unit, frame), a.nrun units -> a.nwork, a.per and *g workgroups: one contiguous range of
+// items per wave, as many waves as the device holds at once
+static int moments_ranges(bb_moments_args &a, size_t nframes, unsigned *g)
+{
+    const uint64_t units = a.nrun;                                            // runs or column blocks
     if (a.nseg > (~0ull) / (uint64_t)nframes || a.nseg * (uint64_t)nframes > (~0ull) / units) return BB_ERANGE;
     a.nwork = a.nseg * (uint64_t)nframes * units;
-    // one contiguous range of items per wave, as many waves as the device holds at once
     const uint64_t waves = std::min<uint64_t>(a.nwork, BB_MOMENTS_GRID * BB_WAVES_PER_BLOCK);
     a.per = (a.nwork + waves - 1) / waves;
     const uint64_t ranges = (a.nwork + a.per - 1) / a.per;
-    const uint64_t g = (ranges + BB_WAVES_PER_BLOCK - 1) / BB_WAVES_PER_BLOCK;
-    hipLaunchKernelGGL(k_i8_moments, dim3((unsigned)g), dim3(BB_BLOCK), 0, (hipStream_t)stream, a);
+    *g = (unsigned)((ranges + BB_WAVES_PER_BLOCK - 1) / BB_WAVES_PER_BLOCK);
+    return BB_OK;
+}
+
+int bb_i8_moments(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size_t nframes,
+                  const bb_moments_params *p, int64_t *d_sums, size_t sums_elems, void *stream)
+{
+    bb_moments_args a;
+    uint64_t nrows;
+    unsigned g;
+    int rc = moments_params_check(p, &a);
+    if (rc) return rc;
+    rc = moments_request(a, p, d_buf, buf_nbytes, d_src, nframes, d_sums, sums_elems, 2 * (uint64_t)a.bin_elems, &nrows);
+    if (rc || !nrows) return rc;
+    if (a.P) {
+        a.mode = BB_MOM_RUN;
+        moments_run_split(a);
+    } else {
+        const bool v4 = a.Rb % 16 == 0 && moments_wide(p, d_buf, d_src);
+        a.mode = v4 ? BB_MOM_ROW4 : BB_MOM_ROW1;
+        moments_rows_split(a, a.Rb / (v4 ? 16u : 4u));
+    }
+    rc = moments_ranges(a, nframes, &g);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_i8_moments, dim3(g), dim3(BB_BLOCK), 0, (hipStream_t)stream, a);
     BB_NOTE("k_i8_moments<%s> grid %u items %llu", a.mode == BB_MOM_RUN ? "run" : a.mode == BB_MOM_ROW4 ? "rows16" : "rows4",
-            (unsigned)g, (unsigned long long)a.nwork);
+            g, (unsigned long long)a.nwork);
+    BB_HIP(hipGetLastError());
+    return BB_OK;
+}
+
+// ---- cross-polarisation products per channel and time bin (k_coherence.h).  EXTENSION: no reference
+//      counterpart.  The parameter block, the frame, first_row and bin rules are those of bb_i8_moments. ----
+static int coherence_params_check(const bb_moments_params *p, bb_moments_args *a)
+{
+    const int rc = moments_params_check(p, a);
+    if (rc) return rc;
+    if (p->npol != 2 || p->ncomp != 2) return BB_ENOTSUP;                     // X and Y, both complex
+    if (p->layout == BB_MOMENTS_ROWS && p->nchan > 1 && (p->nchan & 1)) return BB_ENOTSUP;   // the Y half begins inside a dword
+    return BB_OK;
+}
+
+int bb_i8_coherence_check(const bb_moments_params *p) { bb_moments_args a; return coherence_params_check(p, &a); }
+
+int bb_i8_coherence(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size_t nframes,
+                    const bb_moments_params *p, int64_t *d_sums, size_t sums_elems, void *stream)
+{
+    bb_moments_args a;
+    uint64_t nrows;
+    unsigned g;
+    int rc = coherence_params_check(p, &a);
+    if (rc) return rc;
+    rc = moments_request(a, p, d_buf, buf_nbytes, d_src, nframes, d_sums, sums_elems, 4 * (uint64_t)a.nchan, &nrows);
+    if (rc || !nrows) return rc;
+    if (a.P) {                                                                // 4: a run of quads per channel
+        a.mode = BB_COH_RUN;
+        moments_run_split(a);
+    } else if (p->layout == BB_MOMENTS_GUPPI_TF) {                            // rows of nchan quads
+        const bool v4 = a.Rb % 16 == 0 && moments_wide(p, d_buf, d_src);
+        a.mode = v4 ? BB_COH_ROW4 : BB_COH_ROW1;
+        moments_rows_split(a, a.Rb / (v4 ? 16u : 4u));
+    } else {                                                                  // rows of an X and a Y half: lane columns of the X half
+        const bool v4 = a.Rb % 32 == 0 && moments_wide(p, d_buf, d_src);
+        a.mode = v4 ? BB_COH_SPLIT4 : BB_COH_SPLIT1;
+        moments_rows_split(a, a.Rb / (v4 ? 32u : 8u));
+    }
+    rc = moments_ranges(a, nframes, &g);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_i8_coherence, dim3(g), dim3(BB_BLOCK), 0, (hipStream_t)stream, a);
+    static const char *const shape[] = {"run", "rows4", "rows16", "split4", "split16"};
+    BB_NOTE("k_i8_coherence<%s> grid %u items %llu", shape[a.mode], g, (unsigned long long)a.nwork);
     BB_HIP(hipGetLastError());
     return BB_OK;
 }

@@ -19,6 +19,7 @@
 #include "k_recode.h"
 #include "k_recode_tables.h"
 #include "k_moments.h"
+#include "k_coherence.h"
 #include "k_tfpick.h"
 #if BB_EXP
 #include "k_burst.h"

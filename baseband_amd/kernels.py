@@ -680,6 +680,32 @@ def i8_moments(dbuf, nframes, layout, npol, nchan, ncomp, ntime, t_lo, t_hi, bin
     return sums
 
 
+def i8_coherence_supported(layout, nchan, ntime, t_lo=0, t_hi=None, bin_rows=1, src0=0, src_stride=0):
+    """Would `i8_coherence` take this geometry of two complex polarisations?  (bb_i8_coherence_check; no
+    device needed.)"""
+    if t_hi is None:
+        t_hi = ntime
+    if not _fits(layout, 2, nchan, 2, ntime, t_lo, t_hi, bin_rows, src0, src_stride):
+        return False
+    return _lib.i8_coherence_check(layout, 2, nchan, 2, ntime, t_lo, t_hi, bin_rows, src0, src_stride) == _lib.BB_OK
+
+
+def i8_coherence(dbuf, nframes, layout, nchan, ntime, t_lo, t_hi, bin_rows, nbins, first_row=0,
+                 src0=0, src_stride=0, src=None, sums=None):
+    """Cross-polarisation products per channel and time bin from stored int8 samples of two complex
+    polarisations X, Y (bb_i8_coherence; EXTENSION, no reference counterpart): frames, times, the
+    series of rows and its bins as in `i8_moments` -> int64 device tensor of shape ``(nbins, nchan,
+    4)``, the last axis (sum |X|^2, sum |Y|^2, Re sum X conj(Y), Im sum X conj(Y)).  With `sums`
+    (such a tensor, contiguous) the call ADDS to it.  Nothing is decoded and nothing synchronises."""
+    p = _lib.moments_params(layout, 2, nchan, 2, ntime, t_lo, t_hi, bin_rows, nbins, first_row, src0, src_stride)
+    if not _given(sums, 'sums', torch.int64):
+        check(lib.bb_i8_coherence_check(C.byref(p)), 'bb_i8_coherence')      # (before a shape is made of the parameters)
+        sums = torch.zeros((nbins, nchan, 4), dtype=torch.int64, device=dbuf.device)
+    check(lib.bb_i8_coherence(_ptr(dbuf), dbuf.numel(), _ptr(src), nframes, C.byref(p), _ptr(sums), sums.numel(),
+                              _stream(dbuf)), 'bb_i8_coherence')
+    return sums
+
+
 REPACK_MAX_ROW_BITS = 256      # nslot * chunk * bps the repack kernel takes
 REPACK_MAX_SLOTS = 32          # ... and thread slots on either side
 

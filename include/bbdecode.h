@@ -790,6 +790,37 @@ int bb_i8_moments(const void *d_buf, size_t buf_nbytes,
                   int64_t *d_sums, size_t sums_elems, void *stream);
 int bb_i8_moments_check(const bb_moments_params *params);
 
+/*
+ * The cross-polarisation products of two-polarisation complex int8 streams, per
+ * channel and time bin, from the same stored bytes: with X the sample of
+ * polarisation 0 and Y that of polarisation 1, the times of a (bin, channel c)
+ * ADD four int64 values to d_sums[(bin * nchan + c) * 4 + k]:
+ *     k = 0: sum |X|^2 = xr * xr + xi * xi
+ *     k = 1: sum |Y|^2 = yr * yr + yi * yi
+ *     k = 2: sum Re X * conj(Y) = xr * yr + xi * yi
+ *     k = 3: sum Im X * conj(Y) = xi * yr - xr * yi
+ * (the coherency matrix, hence Stokes I, Q, U, V per time and frequency; the
+ * sums of x * x above cannot give k = 2, 3).  Exact for every stored byte, -128
+ * included.  The parameter block, the layouts, the frames, the series of rows,
+ * first_row and the bins are those of bb_i8_moments, and so is the rule that
+ * the caller zeroes d_sums and several calls fill one answer.
+ *
+ * bb_i8_coherence_check answers what bb_i8_moments_check answers, in its order
+ * (BB_MOMENTS_MKBF stays BB_ENOTSUP), and then BB_ENOTSUP for npol != 2, for
+ * ncomp != 2, and for BB_MOMENTS_ROWS with nchan > 1 and odd (the row's Y half
+ * would begin inside a dword): decode and reduce instead.
+ *
+ * The call answers in addition what bb_i8_moments answers, in its order, with
+ * BB_ERANGE when sums_elems < nbins * nchan * 4.  Stream-ordered, never
+ * allocates, never synchronises; nframes == 0 or t_lo == t_hi launches
+ * nothing; an argument error leaves d_sums untouched.
+ */
+int bb_i8_coherence(const void *d_buf, size_t buf_nbytes,
+                    const int64_t *d_src, size_t nframes,
+                    const bb_moments_params *params,
+                    int64_t *d_sums, size_t sums_elems, void *stream);
+int bb_i8_coherence_check(const bb_moments_params *params);
+
 /* ---- format conversion on the packed bytes -------------------------------- */
 
 /*
