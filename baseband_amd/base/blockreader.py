@@ -18,6 +18,15 @@ from ..staging import WindowPipeline
 from .base import GPUStreamReaderBase, _apply_squeeze, _to_host_array
 
 
+def bin_counts(nbins, bin_samples, count, device=None):
+    """Samples in each of the `nbins` bins of `bin_samples` that a request of `count` samples fills
+    (``nbins = ceil(count / bin_samples)``: the last may be short) -> int64 tensor on `device`."""
+    n = torch.full((nbins,), bin_samples, dtype=torch.int64, device=device)
+    if nbins:
+        n[-1] = count - (nbins - 1) * bin_samples
+    return n
+
+
 class BlockStreamReader(GPUStreamReaderBase):
     # subclasses set: _frame_nbytes, _header_nbytes, _file_offset0, _nframes
     def _pieces(self, offset, count):
@@ -173,6 +182,27 @@ class BlockStreamReader(GPUStreamReaderBase):
         return (self._file_offset0 + frame * self._frame_nbytes,
                 self._frame_nbytes)
 
+    def _cut_windows(self, f0, f1, image_nbytes):
+        """The run of frames [f0, f1) in windows of whole frames, as many as `window_bytes` holds and one at
+        the least -> ``(cap, ranges, spans)``: the bytes a window may take, every window's bytes ``(lo, hi)``
+        of the image (the last frame cut at the image's end) and its frames ``(s, e)``."""
+        per_win = max(1, self.window_bytes // self._frame_nbytes)
+        cap = max(per_win * self._frame_nbytes, self._frame_span(f0)[1])
+        ranges, spans = [], []
+        for s in range(f0, f1, per_win):
+            e = min(f1, s + per_win)
+            last_lo, last_n = self._frame_span(e - 1)
+            ranges.append((self._frame_span(s)[0], min(last_lo + last_n, image_nbytes)))
+            spans.append((s, e))
+        return cap, ranges, spans
+
+    def _windows(self, image, f0, f1):
+        """``(ranges, spans)`` of `_cut_windows` for `image`, with `self._pipeline` large enough for them."""
+        cap, ranges, spans = self._cut_windows(f0, f1, len(image))
+        if self._pipeline is None or self._pipeline.cap < cap:
+            self._pipeline = WindowPipeline(image, cap)
+        return ranges, spans
+
     read_through = True     # queue a read-only pass over a request's frames in front of their decode (kernels.touch)
 
     def read(self, count=None, out=None):
@@ -276,18 +306,7 @@ class BlockStreamReader(GPUStreamReaderBase):
                                     self._header_nbytes, self._frame_nbytes, f0)
                 done += (f1 - f0) * (b - a)
                 continue
-            off0, nbytes = self._frame_span(f0)
-            per_win = max(1, self.window_bytes // self._frame_nbytes)
-            cap = max(per_win * self._frame_nbytes, nbytes)
-            if self._pipeline is None or self._pipeline.cap < cap:
-                self._pipeline = WindowPipeline(image, cap)
-            ranges, spans = [], []
-            for s in range(f0, f1, per_win):
-                e = min(f1, s + per_win)
-                lo = self._frame_span(s)[0]
-                last_lo, last_n = self._frame_span(e - 1)
-                ranges.append((lo, min(last_lo + last_n, len(image))))
-                spans.append((s, e))
+            ranges, spans = self._windows(image, f0, f1)
             base = done
 
             def process(dbuf, i, base=base, a=a, b=b, f0=f0):
@@ -377,18 +396,7 @@ class BlockStreamReader(GPUStreamReaderBase):
             elif f1 == f0 + 1 and self._ahead is not None and self._ahead[0] == f0:
                 add(self._ahead[1], 1, a, b, nt, done)      # the frame that small reads keep staged
             else:
-                nbytes = self._frame_span(f0)[1]
-                per_win = max(1, self.window_bytes // self._frame_nbytes)
-                cap = max(per_win * self._frame_nbytes, nbytes)
-                if self._pipeline is None or self._pipeline.cap < cap:
-                    self._pipeline = WindowPipeline(image, cap)
-                ranges, spans = [], []
-                for s in range(f0, f1, per_win):
-                    e = min(f1, s + per_win)
-                    lo = self._frame_span(s)[0]
-                    last_lo, last_n = self._frame_span(e - 1)
-                    ranges.append((lo, min(last_lo + last_n, len(image))))
-                    spans.append((s, e))
+                ranges, spans = self._windows(image, f0, f1)
 
                 def process(dbuf, i, base=done, a=a, b=b, nt=nt, f0=f0):
                     s, e = spans[i]
@@ -397,6 +405,38 @@ class BlockStreamReader(GPUStreamReaderBase):
                 self._pipeline.run(ranges, process)
             done += (f1 - f0) * (b - a)
         assert done == count
+
+    def _series_request(self, name, bin_samples, count, check=None):
+        """What `moment_series` and `coherence_series` (`name`) check before anything else, in this order:
+        the stream is open, `bin_samples`, int8 samples, `check()` (what else the method asks of the
+        stream), `count`, a GPU -> ``(bin_samples, count, nbins)`` as plain numbers, and what `check`
+        returned.  `power_series` and `stokes_series` ask it too, for the samples of their bins."""
+        if self.closed:
+            raise ValueError("I/O operation on closed stream.")
+        bin_samples = operator.index(bin_samples)
+        if bin_samples < 1:
+            raise ValueError(name + ": bin_samples must be at least 1")
+        if self.bps != 8:
+            raise NotImplementedError("{}: samples of {} bits are not int8".format(name, self.bps))
+        checked = check() if check is not None else None
+        left = self.shape[0] - self.offset
+        if count is None or count < 0:
+            count = max(0, left)
+        if count > left:
+            raise EOFError("cannot read from beyond end of input.")
+        kernels.require_gpu()
+        return bin_samples, count, -(-count // bin_samples), checked
+
+    def _series_plan(self, name, plan_of, bin_samples, packed):
+        """``plan_of(bin_samples)`` where the kernel serves the request, None where the fallback does:
+        with ``packed=False``, and where the plan is a str, the reason why the kernel does not take the
+        stream -- which ``packed=True`` raises as `NotImplementedError`."""
+        plan = None if packed is False else plan_of(bin_samples)
+        if isinstance(plan, str):
+            if packed:
+                raise NotImplementedError(name + ": " + plan)
+            plan = None
+        return plan
 
     def moment_series(self, bin_samples, count=None, packed=None):
         """Sum of x and sum of x * x of every real component per time bin, over the samples
@@ -413,25 +453,8 @@ class BlockStreamReader(GPUStreamReaderBase):
         elsewhere (MKBF heaps, real GUPPI samples, samples of 6 bytes, payloads off a dword);
         both are exact.  ``packed=False`` always reads and reduces, ``packed=True`` raises
         `NotImplementedError` where the kernel does not take the stream."""
-        if self.closed:
-            raise ValueError("I/O operation on closed stream.")
-        bin_samples = operator.index(bin_samples)
-        if bin_samples < 1:
-            raise ValueError("moment_series: bin_samples must be at least 1")
-        if self.bps != 8:
-            raise NotImplementedError("moment_series: samples of {} bits are not int8".format(self.bps))
-        left = self.shape[0] - self.offset
-        if count is None or count < 0:
-            count = max(0, left)
-        if count > left:
-            raise EOFError("cannot read from beyond end of input.")
-        kernels.require_gpu()
-        nbins = -(-count // bin_samples)
-        plan = None if packed is False else self._moments_plan(bin_samples)
-        if isinstance(plan, str):
-            if packed:
-                raise NotImplementedError("moment_series: " + plan)
-            plan = None
+        bin_samples, count, nbins, _ = self._series_request('moment_series', bin_samples, count)
+        plan = self._series_plan('moment_series', self._moments_plan, bin_samples, packed)
         if plan is None:
             return self._moments_by_read(bin_samples, count, nbins)
         layout, npol, nchan, ncomp = plan
@@ -495,16 +518,11 @@ class BlockStreamReader(GPUStreamReaderBase):
         of shape ``(nbins,) + sample_shape``: the sum of x * x over the components of a bin,
         divided by the number of samples in it.  Name and meaning are those of the VDIF and
         Mark 5B method; `packed` as in `moment_series`."""
-        m = self.moment_series(bin_samples, count, packed)
-        nbins = m.shape[0]
-        left = self.shape[0] - self.offset
-        count = max(0, left) if count is None or count < 0 else count
-        sq = m[..., 1]
+        bin_samples, count, nbins, _ = self._series_request('moment_series', bin_samples, count)
+        sq = self.moment_series(bin_samples, count, packed)[..., 1]
         if self.complex_data:
             sq = sq.sum(-1)
-        n = torch.full((nbins,), operator.index(bin_samples), dtype=torch.int64, device=m.device)
-        if nbins:
-            n[-1] = count - (nbins - 1) * operator.index(bin_samples)
+        n = bin_counts(nbins, bin_samples, count, sq.device)
         return sq.double() / n.double().reshape((nbins,) + (1,) * (sq.dim() - 1))
 
     # -- cross-polarisation products per channel and time bin from the stored int8 bytes (kernels.i8_coherence)
@@ -559,26 +577,9 @@ class BlockStreamReader(GPUStreamReaderBase):
         channels above one in plain DADA, payloads off a dword, real samples: X * Y, then 0);
         both are exact.  ``packed=False`` always reads and reduces, ``packed=True`` raises
         `NotImplementedError` where the kernel does not take the stream."""
-        if self.closed:
-            raise ValueError("I/O operation on closed stream.")
-        bin_samples = operator.index(bin_samples)
-        if bin_samples < 1:
-            raise ValueError("coherence_series: bin_samples must be at least 1")
-        if self.bps != 8:
-            raise NotImplementedError("coherence_series: samples of {} bits are not int8".format(self.bps))
-        chans = self._coherence_channels()
-        left = self.shape[0] - self.offset
-        if count is None or count < 0:
-            count = max(0, left)
-        if count > left:
-            raise EOFError("cannot read from beyond end of input.")
-        kernels.require_gpu()
-        nbins = -(-count // bin_samples)
-        plan = None if packed is False else self._coherence_plan(bin_samples)
-        if isinstance(plan, str):
-            if packed:
-                raise NotImplementedError("coherence_series: " + plan)
-            plan = None
+        bin_samples, count, nbins, chans = self._series_request('coherence_series', bin_samples, count,
+                                                                check=self._coherence_channels)
+        plan = self._series_plan('coherence_series', self._coherence_plan, bin_samples, packed)
         if plan is None:
             return self._coherence_by_read(bin_samples, count, nbins, chans.shape)
         layout, nchan = plan
@@ -612,13 +613,9 @@ class BlockStreamReader(GPUStreamReaderBase):
         """``(XX + YY, XX - YY, 2 Re, 2 Im)`` of `coherence_series` (XX, YY, Re, Im its last axis),
         divided by the number of samples in the bin (the last bin may be short) -> float64
         device tensor of the same shape."""
-        c = self.coherence_series(bin_samples, count, packed)
-        nbins = c.shape[0]
-        left = self.shape[0] - self.offset
-        count = max(0, left) if count is None or count < 0 else count
-        n = torch.full((nbins,), operator.index(bin_samples), dtype=torch.int64, device=c.device)
-        if nbins:
-            n[-1] = count - (nbins - 1) * operator.index(bin_samples)
-        xx, yy, re, im = c.unbind(-1)
+        bin_samples, count, nbins, _ = self._series_request('coherence_series', bin_samples, count,
+                                                            check=self._coherence_channels)
+        xx, yy, re, im = self.coherence_series(bin_samples, count, packed).unbind(-1)
         s = torch.stack((xx + yy, xx - yy, 2 * re, 2 * im), -1)
+        n = bin_counts(nbins, bin_samples, count, s.device)
         return s.double() / n.double().reshape((nbins,) + (1,) * (s.dim() - 1))

@@ -554,12 +554,24 @@ static int moments_ranges(bb_moments_args &a, size_t nframes, unsigned *g)
     return BB_OK;
 }
 
+// What both entries do once the split is made: the wave ranges, the launch, the note of bb_last_kernel.
+static int moments_launch(bb_moments_args &a, size_t nframes, void (*kernel)(bb_moments_args), const char *name,
+                          const char *shape, void *stream)
+{
+    unsigned g;
+    const int rc = moments_ranges(a, nframes, &g);
+    if (rc) return rc;
+    hipLaunchKernelGGL(kernel, dim3(g), dim3(BB_BLOCK), 0, (hipStream_t)stream, a);
+    BB_NOTE("%s<%s> grid %u items %llu", name, shape, g, (unsigned long long)a.nwork);
+    BB_HIP(hipGetLastError());
+    return BB_OK;
+}
+
 int bb_i8_moments(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size_t nframes,
                   const bb_moments_params *p, int64_t *d_sums, size_t sums_elems, void *stream)
 {
     bb_moments_args a;
     uint64_t nrows;
-    unsigned g;
     int rc = moments_params_check(p, &a);
     if (rc) return rc;
     rc = moments_request(a, p, d_buf, buf_nbytes, d_src, nframes, d_sums, sums_elems, 2 * (uint64_t)a.bin_elems, &nrows);
@@ -572,13 +584,8 @@ int bb_i8_moments(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, si
         a.mode = v4 ? BB_MOM_ROW4 : BB_MOM_ROW1;
         moments_rows_split(a, a.Rb / (v4 ? 16u : 4u));
     }
-    rc = moments_ranges(a, nframes, &g);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_i8_moments, dim3(g), dim3(BB_BLOCK), 0, (hipStream_t)stream, a);
-    BB_NOTE("k_i8_moments<%s> grid %u items %llu", a.mode == BB_MOM_RUN ? "run" : a.mode == BB_MOM_ROW4 ? "rows16" : "rows4",
-            g, (unsigned long long)a.nwork);
-    BB_HIP(hipGetLastError());
-    return BB_OK;
+    return moments_launch(a, nframes, k_i8_moments, "k_i8_moments",
+                          a.mode == BB_MOM_RUN ? "run" : a.mode == BB_MOM_ROW4 ? "rows16" : "rows4", stream);
 }
 
 // ---- cross-polarisation products per channel and time bin (k_coherence.h).  EXTENSION: no reference
@@ -599,7 +606,6 @@ int bb_i8_coherence(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, 
 {
     bb_moments_args a;
     uint64_t nrows;
-    unsigned g;
     int rc = coherence_params_check(p, &a);
     if (rc) return rc;
     rc = moments_request(a, p, d_buf, buf_nbytes, d_src, nframes, d_sums, sums_elems, 4 * (uint64_t)a.nchan, &nrows);
@@ -616,11 +622,6 @@ int bb_i8_coherence(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, 
         a.mode = v4 ? BB_COH_SPLIT4 : BB_COH_SPLIT1;
         moments_rows_split(a, a.Rb / (v4 ? 32u : 8u));
     }
-    rc = moments_ranges(a, nframes, &g);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_i8_coherence, dim3(g), dim3(BB_BLOCK), 0, (hipStream_t)stream, a);
     static const char *const shape[] = {"run", "rows4", "rows16", "split4", "split16"};
-    BB_NOTE("k_i8_coherence<%s> grid %u items %llu", shape[a.mode], g, (unsigned long long)a.nwork);
-    BB_HIP(hipGetLastError());
-    return BB_OK;
+    return moments_launch(a, nframes, k_i8_coherence, "k_i8_coherence", shape[a.mode], stream);
 }

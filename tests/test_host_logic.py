@@ -1528,3 +1528,47 @@ def test_frame_set_rules_of_the_located_frame_index():
     recs = rules(dev, offs, recs)
     ok = ((recs[:, 3] >> 16) & _lib.FRAME_OK) != 0
     assert bool(ok.all())
+
+
+@pytest.mark.parametrize('bin_samples,count,expected', [
+    (4, 0, []),                      # nothing asked for: no bin
+    (4, 12, [4, 4, 4]),              # a multiple of the bin: all bins equal
+    (4, 9, [4, 4, 1]),               # 2 * bin + 1: a last bin of one sample
+    (7, 5, [5]),                     # a bin longer than the request: one bin of `count`
+])
+def test_bin_counts_of_a_series_request(bin_samples, count, expected):
+    """The samples per bin that `power_series` and `stokes_series` of the block readers divide by."""
+    from baseband_amd.base.blockreader import bin_counts
+    import torch
+    n = bin_counts(-(-count // bin_samples), bin_samples, count)
+    assert n.dtype == torch.int64 and n.tolist() == expected and int(n.sum()) == count
+
+
+def test_block_reader_window_cut_without_a_device():
+    """`BlockStreamReader._cut_windows`: a run of frames in windows of whole frames -> the pipeline's capacity,
+    the windows' bytes of the image and their frames (what `read()` and the series methods stage)."""
+    import types
+    from baseband_amd.base.blockreader import BlockStreamReader as R
+
+    def stub(frame_nbytes, window_bytes, offset0=0):
+        r = types.SimpleNamespace(_frame_nbytes=frame_nbytes, window_bytes=window_bytes, _file_offset0=offset0)
+        r._frame_span = lambda frame: R._frame_span(r, frame)
+        return r
+    # 7 frames at 3 per window (3.5 frames fit), the run begins at frame 2 of a file whose frames begin at byte 16
+    r = stub(1000, 3500, offset0=16)
+    cap, ranges, spans = R._cut_windows(r, 2, 9, 10 ** 6)
+    assert cap == 3000
+    assert spans == [(2, 5), (5, 8), (8, 9)]
+    assert [(s - 2, e - 2) for s, e in spans] == [(0, 3), (3, 6), (6, 7)]
+    assert ranges == [(2016, 5016), (5016, 8016), (8016, 9016)]
+    # the image ends 300 bytes into the last frame: that window is cut there, the others are whole
+    cap, ranges, spans = R._cut_windows(r, 0, 7, 6316)
+    assert cap == 3000 and spans == [(0, 3), (3, 6), (6, 7)]
+    assert ranges == [(16, 3016), (3016, 6016), (6016, 6316)]
+    # a frame larger than a window: one frame per window, and a window holds the frame
+    r = stub(5000, 3500)
+    cap, ranges, spans = R._cut_windows(r, 1, 4, 10 ** 6)
+    assert cap == 5000
+    assert spans == [(1, 2), (2, 3), (3, 4)] and ranges == [(5000, 10000), (10000, 15000), (15000, 20000)]
+    # an empty run stages nothing
+    assert R._cut_windows(r, 3, 3, 10 ** 6)[1:] == ([], [])
