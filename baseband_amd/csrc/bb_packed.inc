@@ -73,6 +73,42 @@ inline dim3 tables_grid(uint64_t nwork, size_t lds)
 {
     return capped_grid((nwork + BB_WAVES_PER_BLOCK - 1) / BB_WAVES_PER_BLOCK, 4ull * 256ull * std::min<uint64_t>(8, (160ull << 10) / lds));
 }
+
+// What bb_repack_frames and both recode entries do after the parameter check: the output check, the source check and
+// the overflow of the item count, in this order, and the members that the arguments of k_repack, k_recode and
+// k_recode_tables name alike (the item geometry and the staging read them).  Params: bb_repack_params or bb_recode_params, which name
+// what is read here alike; an item has item_bits bits on its wider side.  a.nwork == 0: nothing is asked for.
+template <class Args, class Params>
+inline int piece_args(Args &a, const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size_t nframes,
+                      const Params *p, int bps_in, int bps_out, uint64_t R_in, uint64_t R_out, void *d_out, size_t out_nbytes,
+                      uint32_t item_bits)
+{
+    packed_out o;
+    a.nwork = 0;
+    const uint64_t bi = (uint64_t)p->chunk_in * (uint64_t)bps_in, bo = (uint64_t)p->chunk_out * (uint64_t)bps_out;   // bits per row and slot
+    int rc = packed_output(d_out, out_nbytes, nframes, p->payload_in, R_in, R_out, p->payload_out, (uint64_t)p->nslot_out, bi, bo,
+                           p->row_lo, p->row_hi, p->first_row, &o);
+    if (rc || !o.nrows) return rc;
+    rc = packed_source(a, d_buf, buf_nbytes, d_src, p->src0, p->src_stride,
+                       (uint64_t)nframes * (uint64_t)p->nslot_in, p->payload_in);
+    if (rc) return rc;
+    a.out = (uint8_t *)d_out;
+    a.buf_n = buf_nbytes;
+    a.pay_in = p->payload_in; a.pay_out = p->payload_out;
+    a.row_lo = p->row_lo; a.first_row = p->first_row; a.nrows = o.nrows;
+    a.R_out = R_out;
+    a.F0 = p->first_row / R_out;
+    a.nslot_in = (uint32_t)p->nslot_in; a.nslot_out = (uint32_t)p->nslot_out;
+    a.lbi = ceil_log2(bi); a.lbo = ceil_log2(bo);
+    // at least 256 rows of 8 KiB, 128 of 4 KiB: 16 bytes or more of every slot on either side
+    a.T = item_bits / ((uint32_t)p->nslot_in * (uint32_t)p->chunk_in * (uint32_t)std::max(bps_in, bps_out));
+    a.sstride = ((a.T << a.lbi) >> 3) + BB_REPACK_SLACK;
+    a.nseg = (R_out + a.T - 1) / a.T;
+    const uint64_t nf = o.f_last - a.F0 + 1;
+    if (nf > (~0ull) / a.nseg) return BB_ERANGE;
+    a.nwork = nf * a.nseg;
+    return BB_OK;
+}
 } }
 
 // ---- sampler statistics (k_states.h).  EXTENSION: no reference counterpart. ----
@@ -241,31 +277,12 @@ int bb_repack_check(const bb_repack_params *p) { uint64_t R_in, R_out; return re
 int bb_repack_frames(const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size_t nframes,
                      const bb_repack_params *p, void *d_out, size_t out_nbytes, void *stream)
 {
-    uint64_t R_in, R_out; packed_out o;
+    uint64_t R_in, R_out;
     int rc = repack_params_check(p, &R_in, &R_out);
     if (rc) return rc;
-    const uint64_t bi = (uint64_t)p->chunk_in * (uint64_t)p->bps, bo = (uint64_t)p->chunk_out * (uint64_t)p->bps;   // bits per row and slot
-    rc = packed_output(d_out, out_nbytes, nframes, p->payload_in, R_in, R_out, p->payload_out, (uint64_t)p->nslot_out, bi, bo,
-                       p->row_lo, p->row_hi, p->first_row, &o);
-    if (rc || !o.nrows) return rc;
     bb_repack_args a;
-    rc = packed_source(a, d_buf, buf_nbytes, d_src, p->src0, p->src_stride,
-                       (uint64_t)nframes * (uint64_t)p->nslot_in, p->payload_in);
-    if (rc) return rc;
-    a.out = (uint8_t *)d_out;
-    a.buf_n = buf_nbytes;
-    a.pay_in = p->payload_in; a.pay_out = p->payload_out;
-    a.row_lo = p->row_lo; a.first_row = p->first_row; a.nrows = o.nrows;
-    a.R_out = R_out;
-    a.F0 = p->first_row / R_out;
-    a.nslot_in = (uint32_t)p->nslot_in; a.nslot_out = (uint32_t)p->nslot_out;
-    a.lbi = ceil_log2(bi); a.lbo = ceil_log2(bo);
-    a.T = BB_REPACK_ITEM_BITS / (uint32_t)(bi * a.nslot_in);                  // at least 256 rows: 16 bytes or more of every slot
-    a.sstride = ((a.T << a.lbi) >> 3) + BB_REPACK_SLACK;
-    a.nseg = (R_out + a.T - 1) / a.T;
-    const uint64_t nf = o.f_last - a.F0 + 1;
-    if (nf > (~0ull) / a.nseg) return BB_ERANGE;
-    a.nwork = nf * a.nseg;
+    rc = piece_args(a, d_buf, buf_nbytes, d_src, nframes, p, p->bps, p->bps, R_in, R_out, d_out, out_nbytes, BB_REPACK_ITEM_BITS);
+    if (rc || !a.nwork) return rc;
     a.map = (uint32_t)repack_code_map(p->coder_in, p->coder_out, p->bps);
     a.fillw = fill_word(p->fill_code, p->bps);
     // chunks of min(bi, bo) bits stay together; equal slot structures are a stream of whole dwords
@@ -359,42 +376,19 @@ static int recode_params_check(const bb_recode_params *p, uint64_t *R_in, uint64
 
 int bb_recode_check(const bb_recode_params *p) { uint64_t R_in, R_out; return recode_params_check(p, &R_in, &R_out); }
 
-// What both recode entries do after the parameter check: the output and source checks of bb_recode_frames,
-// in its order, and the members every recode kernel's arguments share.  a.nwork == 0: nothing is asked for.
+// What both recode entries do after the parameter check: piece_args, and the members only the recode kernels have.
 extern "C++" { namespace {
 template <class Args>
 inline int recode_args(Args &a, const void *d_buf, size_t buf_nbytes, const int64_t *d_src, size_t nframes,
                        const bb_recode_params *p, uint64_t R_in, uint64_t R_out, void *d_out, size_t out_nbytes,
                        uint32_t item_bits)
 {
-    packed_out o;
-    a.nwork = 0;
-    const uint64_t bi = (uint64_t)p->chunk_in * (uint64_t)p->bps_in, bo = (uint64_t)p->chunk_out * (uint64_t)p->bps_out;   // bits per row and slot
-    int rc = packed_output(d_out, out_nbytes, nframes, p->payload_in, R_in, R_out, p->payload_out, (uint64_t)p->nslot_out, bi, bo,
-                           p->row_lo, p->row_hi, p->first_row, &o);
-    if (rc || !o.nrows) return rc;
-    rc = packed_source(a, d_buf, buf_nbytes, d_src, p->src0, p->src_stride,
-                       (uint64_t)nframes * (uint64_t)p->nslot_in, p->payload_in);
-    if (rc) return rc;
-    a.out = (uint8_t *)d_out;
-    a.buf_n = buf_nbytes;
-    a.pay_in = p->payload_in; a.pay_out = p->payload_out;
-    a.row_lo = p->row_lo; a.first_row = p->first_row; a.nrows = o.nrows;
-    a.R_out = R_out;
-    a.F0 = p->first_row / R_out;
-    a.nslot_in = (uint32_t)p->nslot_in; a.nslot_out = (uint32_t)p->nslot_out;
-    a.lbi = ceil_log2(bi); a.lbo = ceil_log2(bo);
+    const int rc = piece_args(a, d_buf, buf_nbytes, d_src, nframes, p, p->bps_in, p->bps_out, R_in, R_out, d_out, out_nbytes, item_bits);
+    if (rc || !a.nwork) return rc;
     a.lpi = (uint32_t)log2_bps(p->bps_in); a.lpo = (uint32_t)log2_bps(p->bps_out);
-    // the wider side of an item is item_bits (k_recode: 8 KiB; at least 256 rows: 32 bytes or more of every slot on either side)
-    a.T = item_bits / ((uint32_t)p->nslot_in * (uint32_t)p->chunk_in * (uint32_t)std::max(p->bps_in, p->bps_out));
-    a.sstride = ((a.T << a.lbi) >> 3) + BB_REPACK_SLACK;
-    a.nseg = (R_out + a.T - 1) / a.T;
-    const uint64_t nf = o.f_last - a.F0 + 1;
-    if (nf > (~0ull) / a.nseg) return BB_ERANGE;
     // the codes that stay adjacent on both sides, as far as a dword of either side holds them
     a.lgc = std::min(std::min(ceil_log2((uint32_t)p->chunk_in), ceil_log2((uint32_t)p->chunk_out)), std::min(5u - a.lpi, 5u - a.lpo));
     a.fill = (uint32_t)p->fill_code;
-    a.nwork = nf * a.nseg;
     return BB_OK;
 }
 } }

@@ -7,9 +7,10 @@
 // are LSB first; a slot's payloads, frame after frame, are one bit stream in which row r begins
 // at bit r * chunk * bps.
 //
-// Shape (gfx950), k_repack's two phases: a work item is a run of T rows of one OUTPUT frame
-// across all slots, 8 KiB on its wider side, and belongs to one wave.
-//   1. Every input slot's piece of the item goes to LDS as it lies in its stream, UNMAPPED:
+// Shape (gfx950), k_repack's two phases: a work item (k_repack's: bb_repack_items) is a run of T
+// rows of one OUTPUT frame across all slots, 8 KiB on its wider side, and belongs to one wave.
+//   1. The shared staging (bb_stage_pieces in k_repack.h, with bb_recode_stage).
+//      Every input slot's piece of the item goes to LDS as it lies in its stream, UNMAPPED:
 //      16-byte pieces on the stream's own 16-byte grid, one per lane, read as one 16-byte load
 //      from the address aligned down to a dword plus the dword behind it, the misalignment
 //      shifted out in registers; one spare dword per 32 (bb_repack_sw).  Pieces that meet the
@@ -65,17 +66,20 @@ struct bb_recode_geo {
     uint32_t phase, lbi, lbo, sstride, lgc, fill;
 };
 
-// map[c]; s_map: the table in LDS (8-bit codes only).
-template <int LPI>
-__device__ __forceinline__ uint32_t bb_recode_map(const bb_recode_args &a, const uint8_t *s_map, uint32_t c)
-{
-    if constexpr (LPI == 3) return s_map[c];
-    else if constexpr (LPI == 2) {
-        const uint32_t lo = (c & 4u) ? a.map[1] : a.map[0], hi = (c & 4u) ? a.map[3] : a.map[2];
-        return (((c & 8u) ? hi : lo) >> ((c & 3u) << 3)) & 0xffu;
+// bb_stage_pieces for k_recode: the pieces stay as they are, a piece or byte without a source
+// leaves nothing, and a lane sets the validity bits of its piece with one LDS atomic OR.
+struct bb_recode_stage {
+    uint32_t *ok;
+    __device__ __forceinline__ uint32_t code(uint32_t x) const { return x; }
+    __device__ __forceinline__ bool absent(uint32_t &) const { return false; }
+    __device__ __forceinline__ void done(uint32_t loff, uint32_t okm) const
+    {
+        if (okm) {
+            const uint32_t dw = loff >> 2;                               // (a multiple of 4: the four bits lie in one word)
+            __hip_atomic_fetch_or(ok + (dw >> 5), okm << (dw & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        }
     }
-    else return (a.map[0] >> (c << 3)) & 0xffu;
-}
+};
 
 // The NC output codes from bit P on of output slot t's piece (P counts from row 0 of the item's
 // grid; NC codes never pass the end of a dword), mapped, from bit 0 of the result on.  A new
@@ -99,7 +103,7 @@ __device__ __forceinline__ uint32_t bb_recode_codes(const bb_recode_args &a, con
             w = in[bb_repack_sw(d)] >> (ibit & 31u);
             valid = (ok[d >> 5] >> (d & 31u)) & 1u;
         }
-        const uint32_t m = bb_recode_map<LPI>(a, s_map, w & MI);
+        const uint32_t m = bb_requant_map<LPI>(a, s_map, w & MI);
         out |= (valid ? m : g.fill) << (n * BO);
         w >>= BI;
     }
@@ -140,104 +144,29 @@ __device__ __forceinline__ void bb_recode_store(const bb_recode_args &a, const u
 }
 
 // The work items of one wave, at one pair of widths.  (The arguments by value: a copy per pair of
-// widths, which the compiler takes apart into registers; one block that all sixteen loops read
-// has more uses than it takes apart, and stays in scratch.)
+// widths, which the compiler takes apart into registers; one block that all sixteen loops read has
+// more uses than it takes apart, and stays in scratch.)
 template <int LPI, int LPO>
 __device__ __forceinline__ void bb_recode_items(const bb_recode_args a, uint32_t *in, uint32_t *ok, const uint8_t *s_map,
                                                 uint32_t wave, uint32_t lane)
 {
-    uint8_t *in8 = reinterpret_cast<uint8_t *>(in);
-    const uint64_t nwaves = (uint64_t)gridDim.x * BB_WAVES_PER_BLOCK;
-
-    for (uint64_t w = (uint64_t)blockIdx.x * BB_WAVES_PER_BLOCK + wave; w < a.nwork; w += nwaves) {
-        // the item: rows [Gs, Gs + Ti) of output frame F, of which [ga, gb) belong to the request
-        const uint64_t Fr = a.nseg == 1 ? w : w / a.nseg;
-        const uint64_t k = w - Fr * a.nseg;
-        const uint64_t F = a.F0 + Fr;
-        const uint64_t Gs = F * a.R_out + k * a.T;
-        const uint64_t left = a.R_out - k * a.T;
-        const uint32_t Ti = left < a.T ? (uint32_t)left : a.T;
-        const uint64_t ga = Gs > a.first_row ? Gs : a.first_row;
-        const uint64_t gb = Gs + Ti < a.first_row + a.nrows ? Gs + Ti : a.first_row + a.nrows;
-        if (ga >= gb) continue;
-        // ... in every input slot's stream: bytes [ia, ib), kept in LDS from byte ibase on
-        const uint64_t ra = a.row_lo + (ga - a.first_row), rb = a.row_lo + (gb - a.first_row);
-        const uint64_t ia = (ra << a.lbi) >> 3, ib = ((rb << a.lbi) + 7u) >> 3;
-        const uint64_t ibase = ia & ~15ull;
-        bb_recode_geo g;
-        g.lbi = a.lbi; g.lbo = a.lbo; g.sstride = a.sstride; g.lgc = a.lgc; g.fill = a.fill;
-        // bit of grid row 0 relative to ibase: (ra - (ga - Gs)) * bits - ibase * 8, modulo 2^32
-        g.phase = (uint32_t)((ra << a.lbi) - (ibase << 3)) - ((uint32_t)(ga - Gs) << a.lbi);
+    bb_repack_items(a, wave, [&](const bb_repack_item &it) __attribute__((always_inline)) {
+        const bb_recode_geo g{it.phase, a.lbi, a.lbo, a.sstride, a.lgc, a.fill};
 
         for (uint32_t i = lane; i < BB_RECODE_OK_WORDS; i += BB_WAVE) ok[i] = 0u;
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
 
         // 1. input pieces -> LDS, and which of their dwords had a source
-        {
-            const uint32_t pps = (uint32_t)((ib - ibase + 15u) >> 4);        // 16-byte pieces per slot
-            const uint32_t total = pps * a.nslot_in;
-            const uint64_t fu = ibase / a.pay_in;                            // (wave-uniform) frame of ibase
-            const uint64_t offu = ibase - fu * a.pay_in;
-            for (uint32_t j = lane; j < total; j += BB_WAVE) {
-                const uint32_t s = j / pps, q = j - s * pps;
-                const uint32_t loff = s * a.sstride + (q << 4);
-                const uint64_t x0 = ibase + ((uint64_t)q << 4);
-                uint64_t f = fu, off = offu + ((uint64_t)q << 4);
-                if (off >= a.pay_in) { const uint64_t d = off / a.pay_in; f += d; off -= d * a.pay_in; }
-                uint32_t okm = 0u;                                           // the piece's dwords that had a source
-                bool fast = x0 >= ia && x0 + 16u <= ib && off + 16u <= a.pay_in;
-                if (fast) {
-                    const int64_t so = bb_src_at(a, f * a.nslot_in + s);
-                    if (bb_src_ok(so, a.src_lim)) {
-                        const uint64_t o = (uint64_t)so + off;
-                        const uint64_t A = o & ~3ull;
-                        const uint32_t sh = (uint32_t)o & 3u;
-                        if (A + (sh ? 20u : 16u) <= a.buf_n) {
-                            const bb_u4p l = *reinterpret_cast<const bb_u4p *>(a.buf + A);
-                            bb_u4 v = bb_u4{l.x, l.y, l.z, l.w};
-                            if (sh) {
-                                const uint32_t e = *reinterpret_cast<const uint32_t *>(a.buf + A + 16u);
-                                v = bb_u4{bb_repack_shift(l.x, l.y, sh), bb_repack_shift(l.y, l.z, sh),
-                                          bb_repack_shift(l.z, l.w, sh), bb_repack_shift(l.w, e, sh)};
-                            }
-                            uint32_t *d = in + bb_repack_sw(loff >> 2);      // (a piece lies inside one run of 32 dwords)
-                            d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-                            okm = 15u;
-                        } else {
-                            fast = false;                                    // the last bytes of the buffer
-                        }
-                    }
-                }
-                if (!fast) {
-                    const uint64_t lo = x0 > ia ? x0 : ia, hi = x0 + 16u < ib ? x0 + 16u : ib;
-#pragma unroll 1
-                    for (uint64_t x = lo; x < hi; ++x) {
-                        const uint64_t fx = x / a.pay_in;
-                        const int64_t so = bb_src_at(a, fx * a.nslot_in + s);
-                        if (!bb_src_ok(so, a.src_lim)) continue;
-                        in8[bb_repack_swb(loff + (uint32_t)(x - x0))] = a.buf[(uint64_t)so + (x - fx * a.pay_in)];
-                        okm |= 1u << ((uint32_t)(x - x0) >> 2);
-                    }
-                }
-                if (okm) {
-                    const uint32_t dw = loff >> 2;                           // (a multiple of 4: the four bits lie in one word)
-                    __hip_atomic_fetch_or(ok + (dw >> 5), okm << (dw & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                }
-            }
-        }
+        bb_stage_pieces(a, it, in, lane, bb_recode_stage{ok});
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
 
-        // 2. LDS -> output pieces: bytes [va, vb) of the bytes the item's grid has per slot
-        {
-            const uint32_t va = (uint32_t)(((ga - Gs) << a.lbo) >> 3), vb = (uint32_t)(((gb - Gs) << a.lbo) >> 3);
-            uint8_t *dst0 = a.out + F * a.nslot_out * a.pay_out + (((k * a.T) << a.lbo) >> 3);   // the grid's place in slot 0's payload
-            bb_recode_store<LPI, LPO>(a, in, ok, s_map, dst0, va, vb, lane, g);
-        }
+        // 2. LDS -> output pieces
+        bb_recode_store<LPI, LPO>(a, in, ok, s_map, it.dst0, it.va, it.vb, lane, g);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
-    }
+    });
 }
 
 __global__ __launch_bounds__(BB_BLOCK, 4)

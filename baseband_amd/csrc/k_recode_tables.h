@@ -6,9 +6,11 @@
 // where the input payload counts nothing it is fill_code, not mapped.  Equal thread structures
 // on both sides are one of the geometries.
 //
-// Shape (gfx950): k_recode's two phases, a wave per work item of 4 or 8 KiB on its wider side (the
-// staging of the input pieces is that kernel's, line for line; k_recode.h itself is left as it
-// is).  What differs is the table:
+// Shape (gfx950): k_recode's two phases, a wave per work item of 4 or 8 KiB on its wider side.  The
+// item loop, the staging and the store loop are WRITTEN OUT here, a copy of what k_repack.h
+// (bb_repack_items, bb_stage_pieces) and k_recode.h (bb_recode_codes, bb_recode_store) hold for
+// k_repack and k_recode: built on those, this kernel is slower on 4-bit input.
+// A fix to that code must be made here too.  What differs from k_recode is the table:
 //   * The ncomp << bps_in table bytes (at most 8 KiB: 32 components of 8 bits) arrive in device
 //     memory -- an argument block cannot hold them -- and every workgroup copies them to LDS
 //     once, before its item loop, dword by dword (ncomp << bps_in is a power of two; the two

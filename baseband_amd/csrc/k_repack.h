@@ -27,6 +27,10 @@
 //      Groups at the edge of the request are stored byte by byte: bytes outside the rows
 //      of the request are never written.
 // Nothing outside the buffer is read.
+// The item loop (bb_repack_items) and phase 1 (bb_stage_pieces<Stage>) are written here for this
+// kernel and k_recode: what a kernel does to a piece on its way in is its Stage type.
+// k_recode_tables does NOT use them: k_recode_tables.h holds its own copy of the item geometry and
+// of the staging, so a fix to either must be made there as well.
 #pragma once
 #include "bb_common.h"
 
@@ -81,18 +85,127 @@ __device__ __forceinline__ uint32_t bb_repack_shift(uint32_t lo, uint32_t hi, ui
     return (uint32_t)(((((uint64_t)hi) << 32) | lo) >> (8u * sh));
 }
 
-// Stream byte x of input slot s, mapped; the fill pattern where its source counts nothing.
-__device__ __forceinline__ uint32_t bb_repack_in_byte(const bb_repack_args &a, uint32_t s, uint64_t x)
+// ---- what k_repack and k_recode share: the item and phase 1.  Their arguments (bb_repack_args,
+//      bb_recode_args) name the members used here alike.  (k_recode_tables.h has its own copy.) ----
+
+// Work item w: rows [Gs, Gs + Ti) of output frame F, of which [ga, gb) belong to the request.
+struct bb_repack_item {
+    uint64_t F, k, Gs, ga, gb;
+    uint64_t ia, ib, ibase;      // ... in every input slot's stream: bytes [ia, ib), kept in LDS from byte ibase on
+    uint32_t phase;              // bit of grid row 0 relative to ibase (may be negative for rows in front of the request: wraps)
+    uint32_t va, vb;             // ... of the bytes the item's grid has per output slot: bytes [va, vb)
+    uint8_t *dst0;               // the grid's place in slot 0's payload
+};
+
+// The item loop of a wave: body(it) for every item of which a row belongs to the request.  (The loop and
+// not a function of w that says "skip": inlined, that carries the item's members around the loop, the
+// compiler forgets their ranges and the kernels' code gets slower)
+template <class Args, class Body>
+__device__ __forceinline__ void bb_repack_items(const Args &a, uint32_t wave, Body body)
 {
-    const uint64_t f = x / a.pay_in;
-    const uint64_t fs = f * a.nslot_in + s;
-    const int64_t so = bb_src_at(a, fs);
-    if (!bb_src_ok(so, a.src_lim)) return a.fillw & 0xffu;
-    return bb_repack_map(a.buf[(uint64_t)so + (x - f * a.pay_in)], a.map) & 0xffu;
+    const uint64_t nwaves = (uint64_t)gridDim.x * BB_WAVES_PER_BLOCK;
+    for (uint64_t w = (uint64_t)blockIdx.x * BB_WAVES_PER_BLOCK + wave; w < a.nwork; w += nwaves) {
+        const uint64_t Fr = a.nseg == 1 ? w : w / a.nseg;
+        const uint64_t k = w - Fr * a.nseg;
+        const uint64_t F = a.F0 + Fr;
+        const uint64_t Gs = F * a.R_out + k * a.T;
+        const uint64_t left = a.R_out - k * a.T;
+        const uint32_t Ti = left < a.T ? (uint32_t)left : a.T;
+        const uint64_t ga = Gs > a.first_row ? Gs : a.first_row;
+        const uint64_t gb = Gs + Ti < a.first_row + a.nrows ? Gs + Ti : a.first_row + a.nrows;
+        if (ga >= gb) continue;
+        const uint64_t ra = a.row_lo + (ga - a.first_row), rb = a.row_lo + (gb - a.first_row);
+        const uint64_t ia = (ra << a.lbi) >> 3, ib = ((rb << a.lbi) + 7u) >> 3;
+        const uint64_t ibase = ia & ~15ull;
+        bb_repack_item it;
+        it.F = F; it.k = k; it.Gs = Gs; it.ga = ga; it.gb = gb; it.ia = ia; it.ib = ib; it.ibase = ibase;
+        // (ra - (ga - Gs)) * bits - ibase * 8, modulo 2^32
+        it.phase = (uint32_t)((ra << a.lbi) - (ibase << 3)) - ((uint32_t)(ga - Gs) << a.lbi);
+        it.va = (uint32_t)(((ga - Gs) << a.lbo) >> 3); it.vb = (uint32_t)(((gb - Gs) << a.lbo) >> 3);
+        it.dst0 = a.out + F * a.nslot_out * a.pay_out + (((k * a.T) << a.lbo) >> 3);
+        body(it);
+    }
 }
 
-// Geometry of an item on the output side: where row 0 of the item's grid lies in the LDS
-// copy of an input slot (bits, may be negative for rows in front of the request: wraps).
+// 1. of the three kernels: input pieces -> LDS.  Every input slot's piece of the item goes to `in`
+// as it lies in its stream, 16-byte pieces on the stream's own 16-byte grid, one per lane, lanes
+// dealt over (slot, piece); pieces that meet the edge of the request, a frame boundary or the
+// last bytes of the buffer go byte by byte.  `Stage` is what differs between the kernels:
+//   code(x)        what a dword (a byte: its low 8 bits) of the source becomes on its way in;
+//   absent(x)      no source: -> true with x the dword (low 8 bits: the byte) to leave, or false: leave nothing;
+//   done(loff, m)  after the piece at LDS byte loff, m: a bit per dword of it that had a source.
+template <class Stage, class Args>
+__device__ __forceinline__ void bb_stage_pieces(const Args &a, const bb_repack_item &it, uint32_t *in, uint32_t lane, const Stage st)
+{
+    uint8_t *in8 = reinterpret_cast<uint8_t *>(in);
+    const uint64_t ia = it.ia, ib = it.ib, ibase = it.ibase;
+    const uint32_t pps = (uint32_t)((ib - ibase + 15u) >> 4);                // 16-byte pieces per slot
+    const uint32_t total = pps * a.nslot_in;
+    const uint64_t fu = ibase / a.pay_in;                                    // (wave-uniform) frame of ibase
+    const uint64_t offu = ibase - fu * a.pay_in;
+    for (uint32_t j = lane; j < total; j += BB_WAVE) {
+        const uint32_t s = j / pps, q = j - s * pps;
+        const uint32_t loff = s * a.sstride + (q << 4);
+        const uint64_t x0 = ibase + ((uint64_t)q << 4);
+        uint64_t f = fu, off = offu + ((uint64_t)q << 4);
+        if (off >= a.pay_in) { const uint64_t d = off / a.pay_in; f += d; off -= d * a.pay_in; }
+        uint32_t okm = 0u;                                                   // the piece's dwords that had a source
+        bool fast = x0 >= ia && x0 + 16u <= ib && off + 16u <= a.pay_in;
+        if (fast) {
+            const int64_t so = bb_src_at(a, f * a.nslot_in + s);
+            if (bb_src_ok(so, a.src_lim)) {
+                const uint64_t o = (uint64_t)so + off;
+                const uint64_t A = o & ~3ull;
+                const uint32_t sh = (uint32_t)o & 3u;
+                if (A + (sh ? 20u : 16u) <= a.buf_n) {
+                    const bb_u4p l = *reinterpret_cast<const bb_u4p *>(a.buf + A);
+                    bb_u4 v = bb_u4{l.x, l.y, l.z, l.w};
+                    if (sh) {
+                        const uint32_t e = *reinterpret_cast<const uint32_t *>(a.buf + A + 16u);
+                        v = bb_u4{bb_repack_shift(l.x, l.y, sh), bb_repack_shift(l.y, l.z, sh),
+                                  bb_repack_shift(l.z, l.w, sh), bb_repack_shift(l.w, e, sh)};
+                    }
+                    uint32_t *d = in + bb_repack_sw(loff >> 2);              // (a piece lies inside one run of 32 dwords)
+                    d[0] = st.code(v.x); d[1] = st.code(v.y); d[2] = st.code(v.z); d[3] = st.code(v.w);
+                    okm = 15u;
+                } else {
+                    fast = false;                                            // the last bytes of the buffer
+                }
+            } else {
+                uint32_t x;
+                uint32_t *d = in + bb_repack_sw(loff >> 2);
+                if (st.absent(x)) { d[0] = x; d[1] = x; d[2] = x; d[3] = x; }
+            }
+        }
+        if (!fast) {
+            const uint64_t lo = x0 > ia ? x0 : ia, hi = x0 + 16u < ib ? x0 + 16u : ib;
+#pragma unroll 1
+            for (uint64_t x = lo; x < hi; ++x) {
+                const uint64_t fx = x / a.pay_in;
+                const int64_t so = bb_src_at(a, fx * a.nslot_in + s);
+                uint32_t b;
+                if (bb_src_ok(so, a.src_lim)) {
+                    b = st.code(a.buf[(uint64_t)so + (x - fx * a.pay_in)]);
+                    okm |= 1u << ((uint32_t)(x - x0) >> 2);
+                } else if (!st.absent(b)) {
+                    continue;
+                }
+                in8[bb_repack_swb(loff + (uint32_t)(x - x0))] = (uint8_t)b;
+            }
+        }
+        st.done(loff, okm);
+    }
+}
+
+// k_repack's: the code map is ALU work on the dwords; a source that counts nothing leaves the fill pattern.
+struct bb_repack_stage {
+    uint32_t map, fillw;
+    __device__ __forceinline__ uint32_t code(uint32_t x) const { return bb_repack_map(x, map); }
+    __device__ __forceinline__ bool absent(uint32_t &x) const { x = fillw; return true; }
+    __device__ __forceinline__ void done(uint32_t, uint32_t) const {}
+};
+
+// What the store loop needs of the item and the arguments.
 struct bb_repack_geo {
     uint32_t phase, lbi, lbo, sstride;
 };
@@ -190,97 +303,24 @@ void k_repack(bb_repack_args a)
     const uint32_t lane = (uint32_t)bb_lane();
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane(bb_wave());
     uint32_t *in = s_in + wave * (BB_REPACK_LDS_WAVE / 4u);
-    uint8_t *in8 = reinterpret_cast<uint8_t *>(in);
-    const uint64_t nwaves = (uint64_t)gridDim.x * BB_WAVES_PER_BLOCK;
-
-    for (uint64_t w = (uint64_t)blockIdx.x * BB_WAVES_PER_BLOCK + wave; w < a.nwork; w += nwaves) {
-        // the item: rows [Gs, Gs + Ti) of output frame F, of which [ga, gb) belong to the request
-        const uint64_t Fr = a.nseg == 1 ? w : w / a.nseg;
-        const uint64_t k = w - Fr * a.nseg;
-        const uint64_t F = a.F0 + Fr;
-        const uint64_t Gs = F * a.R_out + k * a.T;
-        const uint64_t left = a.R_out - k * a.T;
-        const uint32_t Ti = left < a.T ? (uint32_t)left : a.T;
-        const uint64_t ga = Gs > a.first_row ? Gs : a.first_row;
-        const uint64_t gb = Gs + Ti < a.first_row + a.nrows ? Gs + Ti : a.first_row + a.nrows;
-        if (ga >= gb) continue;
-        // ... in every input slot's stream: bytes [ia, ib), kept in LDS from byte ibase on
-        const uint64_t ra = a.row_lo + (ga - a.first_row), rb = a.row_lo + (gb - a.first_row);
-        const uint64_t ia = (ra << a.lbi) >> 3, ib = ((rb << a.lbi) + 7u) >> 3;
-        const uint64_t ibase = ia & ~15ull;
-        bb_repack_geo g;
-        g.lbi = a.lbi; g.lbo = a.lbo; g.sstride = a.sstride;
-        // bit of grid row 0 relative to ibase: (ra - (ga - Gs)) * bits - ibase * 8, modulo 2^32
-        g.phase = (uint32_t)((ra << a.lbi) - (ibase << 3)) - ((uint32_t)(ga - Gs) << a.lbi);
+    bb_repack_items(a, wave, [&](const bb_repack_item &it) __attribute__((always_inline)) {
+        const bb_repack_geo g{it.phase, a.lbi, a.lbo, a.sstride};
 
         // 1. input pieces -> LDS
-        {
-            const uint32_t pps = (uint32_t)((ib - ibase + 15u) >> 4);        // 16-byte pieces per slot
-            const uint32_t total = pps * a.nslot_in;
-            const uint64_t fu = ibase / a.pay_in;                            // (wave-uniform) frame of ibase
-            const uint64_t offu = ibase - fu * a.pay_in;
-            for (uint32_t j = lane; j < total; j += BB_WAVE) {
-                const uint32_t s = j / pps, q = j - s * pps;
-                const uint32_t loff = s * a.sstride + (q << 4);
-                const uint64_t x0 = ibase + ((uint64_t)q << 4);
-                uint64_t f = fu, off = offu + ((uint64_t)q << 4);
-                if (off >= a.pay_in) { const uint64_t d = off / a.pay_in; f += d; off -= d * a.pay_in; }
-                bool fast = x0 >= ia && x0 + 16u <= ib && off + 16u <= a.pay_in;
-                if (fast) {
-                    const uint64_t fs = f * a.nslot_in + s;
-                    const int64_t so = bb_src_at(a, fs);
-                    bb_u4 v;
-                    if (!bb_src_ok(so, a.src_lim)) {
-                        v = bb_u4{a.fillw, a.fillw, a.fillw, a.fillw};
-                    } else {
-                        const uint64_t o = (uint64_t)so + off;
-                        const uint64_t A = o & ~3ull;
-                        const uint32_t sh = (uint32_t)o & 3u;
-                        if (A + (sh ? 20u : 16u) <= a.buf_n) {
-                            const bb_u4p l = *reinterpret_cast<const bb_u4p *>(a.buf + A);
-                            if (sh) {
-                                const uint32_t e = *reinterpret_cast<const uint32_t *>(a.buf + A + 16u);
-                                v = bb_u4{bb_repack_shift(l.x, l.y, sh), bb_repack_shift(l.y, l.z, sh),
-                                          bb_repack_shift(l.z, l.w, sh), bb_repack_shift(l.w, e, sh)};
-                            } else {
-                                v = bb_u4{l.x, l.y, l.z, l.w};
-                            }
-                            v = bb_u4{bb_repack_map(v.x, a.map), bb_repack_map(v.y, a.map),
-                                      bb_repack_map(v.z, a.map), bb_repack_map(v.w, a.map)};
-                        } else {
-                            fast = false;                                    // the last bytes of the buffer
-                        }
-                    }
-                    if (fast) {                                              // (a piece lies inside one run of 32 dwords)
-                        uint32_t *d = in + bb_repack_sw(loff >> 2);
-                        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-                    }
-                }
-                if (!fast) {
-                    const uint64_t lo = x0 > ia ? x0 : ia, hi = x0 + 16u < ib ? x0 + 16u : ib;
-#pragma unroll 1
-                    for (uint64_t x = lo; x < hi; ++x)
-                        in8[bb_repack_swb(loff + (uint32_t)(x - x0))] = (uint8_t)bb_repack_in_byte(a, s, x);
-                }
-            }
-        }
+        bb_stage_pieces(a, it, in, lane, bb_repack_stage{a.map, a.fillw});
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
 
-        // 2. LDS -> output pieces: bytes [va, vb) of the bytes the item's grid has per slot
-        {
-            const uint32_t va = (uint32_t)(((ga - Gs) << a.lbo) >> 3), vb = (uint32_t)(((gb - Gs) << a.lbo) >> 3);
-            uint8_t *dst0 = a.out + F * a.nslot_out * a.pay_out + (((k * a.T) << a.lbo) >> 3);   // the grid's place in slot 0's payload
-            switch (a.lg) {                                                  // (wave-uniform: one kernel, six loops)
-            case 0:  bb_repack_store<0>(in, dst0, a.pay_out, a.nslot_out, va, vb, lane, g); break;
-            case 1:  bb_repack_store<1>(in, dst0, a.pay_out, a.nslot_out, va, vb, lane, g); break;
-            case 2:  bb_repack_store<2>(in, dst0, a.pay_out, a.nslot_out, va, vb, lane, g); break;
-            case 3:  bb_repack_store<3>(in, dst0, a.pay_out, a.nslot_out, va, vb, lane, g); break;
-            case 4:  bb_repack_store<4>(in, dst0, a.pay_out, a.nslot_out, va, vb, lane, g); break;
-            default: bb_repack_store<5>(in, dst0, a.pay_out, a.nslot_out, va, vb, lane, g); break;
-            }
+        // 2. LDS -> output pieces
+        switch (a.lg) {                                                      // (wave-uniform: one kernel, six loops)
+        case 0:  bb_repack_store<0>(in, it.dst0, a.pay_out, a.nslot_out, it.va, it.vb, lane, g); break;
+        case 1:  bb_repack_store<1>(in, it.dst0, a.pay_out, a.nslot_out, it.va, it.vb, lane, g); break;
+        case 2:  bb_repack_store<2>(in, it.dst0, a.pay_out, a.nslot_out, it.va, it.vb, lane, g); break;
+        case 3:  bb_repack_store<3>(in, it.dst0, a.pay_out, a.nslot_out, it.va, it.vb, lane, g); break;
+        case 4:  bb_repack_store<4>(in, it.dst0, a.pay_out, a.nslot_out, it.va, it.vb, lane, g); break;
+        default: bb_repack_store<5>(in, it.dst0, a.pay_out, a.nslot_out, it.va, it.vb, lane, g); break;
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
-    }
+    });
 }

@@ -54,9 +54,9 @@ struct bb_requant_args {
 
 typedef uint32_t bb_u4d __attribute__((ext_vector_type(4), aligned(4)));     // 16 bytes on a dword boundary
 
-// map[c]; s_map: the table in LDS (8-bit codes only).
-template <int LBI>
-__device__ __forceinline__ uint32_t bb_requant_map(const bb_requant_args &a, const uint8_t *s_map, uint32_t c)
+// map[c]; s_map: the table in LDS (8-bit codes only).  Args: bb_requant_args, or k_recode's, which hold `map` alike.
+template <int LBI, class Args>
+__device__ __forceinline__ uint32_t bb_requant_map(const Args &a, const uint8_t *s_map, uint32_t c)
 {
     if constexpr (LBI == 3) return s_map[c];
     else if constexpr (LBI == 2) {
